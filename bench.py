@@ -14,6 +14,23 @@ pixels with the longest chains are still running; longer calls amortise it
 call, profiles/r02/passes_per_call.json).  The image is bit-identical for any
 split of the passes into calls (tests/test_gpu_parity.py).
 
+A plain run does what the headline figure needs and no more: scene set-up,
+`--warmup` steps, the `--steps` timed steps, one JSON line (value,
+ms_per_step, config, the always-on deviation statistics of the timed region).
+`--dump-outputs DIR` adds DIR/<name>.npy of what the timed region left: the
+G-buffer after the last timed step (frame_buffer, squared_luminance,
+sample_count) and the tonemapped frame (rgba), as float32, at most 64 MB (a
+larger frame: the same seeded sample of pixels of each, listed in pixels.npy).
+The inputs (scene, camera, seeds) are functions of the arguments alone, and
+two runs dump the same bits.  Every dumped value is finite: the few room2m
+pixels whose sums the reference's arithmetic makes infinite or NaN are
+written as 0 and flagged in nonfinite.npy (dump_outputs).  The scene is
+generated once into `--scene-dir`, or into the user's cache (then the temp
+directory) where that cannot be written.
+`--full` adds the measurements that take runs of their own: the counter
+passes and the counted calls (Roofline, below; per_sample; deep_pushes) and
+the CPU baseline; `--no-pmc` / `--no-cpu-baseline` drop one of them again.
+
 Multi-GPU (`--gpus N`): one process per GPU.  Without WORLD_SIZE in the
 environment this script starts the N ranks itself (children with RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 set, before any GPU call in
@@ -24,7 +41,7 @@ into rank 0 (rt_reduce_shards, csrc/shards.hip) plus the tonemap.  value =
 samples of all ranks / max-over-ranks wall time.  The host-side barrier and
 the max use a gloo process group (no data moves through it).
 
-Roofline (north_star: "achieved HBM GB/s vs peak"): measured, not modelled.
+Roofline (`--full`; north_star: "achieved HBM GB/s vs peak"): measured, not modelled.
 Before this process touches the GPU (rank 0, N=1), the same render runs in
 child processes under `rocprofv3 --pmc` (FETCH_SIZE; WRITE_SIZE; SQ
 counters), one call of the bench's passes between two tonemap marker
@@ -35,7 +52,7 @@ bytes per sample x the timed samples/s: chip-wide, call-level, <= peak by
 construction of the counters.  The SURVEY §8d algorithmic bytes (which the
 caches serve, mostly) are reported separately as `algorithmic_GBps`.
 
-cpu_baseline: the C oracle (OpenMP) on the host cores of the GPU box on
+cpu_baseline (`--full`): the C oracle (OpenMP) on the host cores on
 BASELINE.md's budget (the full frame x 1 spp; the whole job for the Cornell
 config), beside the reference's own single-core rate measured in the survey
 container.
@@ -125,10 +142,16 @@ def parse_args(argv=None):
     ap.add_argument("--scene", default="room2m")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the rocprofv3 counter passes "
+                         "(roofline), the counted calls (per-sample work, per-kernel detail) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step left (G-buffer, tonemapped frame) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=240.0,
                     help="cap on the CPU baseline (full frame x 1 spp unless predicted above this)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline traffic)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="--full without the rocprofv3 counter passes (roofline traffic)")
     ap.add_argument("--pmc-save", default=None, help="directory to keep the parsed counter summaries in")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)  # internal: the profiled render
     ap.add_argument("--dry-run", action="store_true",
@@ -375,13 +398,86 @@ def roofline_from_pmc(pmc, samples_per_s):
 
 
 # ------------------------------------------------------------------ helpers
+def scene_dirs(args):
+    """Where the generated scene is looked for and, if missing, written: --scene-dir,
+    then (a tree this user cannot write to) the user's cache and the temp directory."""
+    uid = os.getuid() if hasattr(os, "getuid") else 0
+    return [args.scene_dir,
+            os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"),
+                         "isaklm-raytracer_amd", "scenes"),
+            os.path.join(tempfile.gettempdir(), f"isaklm-raytracer_amd-{uid}", "scenes")]
+
+
 def ensure_scene(args, rt):
-    scene_dir = os.path.join(args.scene_dir, args.scene)
-    scene_file = os.path.join(scene_dir, "scene.txt")
-    if not os.path.exists(scene_file):
+    dirs = [os.path.join(d, args.scene) for d in scene_dirs(args)]
+    for scene_dir in dirs:
+        if os.path.exists(os.path.join(scene_dir, "scene.txt")):
+            return os.path.join(scene_dir, "scene.txt")
+    scene_dir, err = dirs[0], None
+    try:
         os.makedirs(scene_dir, exist_ok=True)
         rt.generate_scene(args.scene, scene_dir)
-    return scene_file
+        return os.path.join(scene_dir, "scene.txt")
+    except (OSError, rt.RtError) as e:
+        err = e
+    for scene_dir in dirs[1:]:
+        # (generated beside its place and renamed: scene.txt names its meshes relatively, and a
+        # reader never sees half a scene)
+        part = f"{scene_dir}.part{os.getpid()}"
+        try:
+            os.makedirs(part, exist_ok=True)
+            rt.generate_scene(args.scene, part)
+            try:
+                os.rename(part, scene_dir)
+            except OSError:  # another process put the same scene there first
+                shutil.rmtree(part, ignore_errors=True)
+            if os.path.exists(os.path.join(scene_dir, "scene.txt")):
+                return os.path.join(scene_dir, "scene.txt")
+        except (OSError, rt.RtError) as e:
+            err = e
+            shutil.rmtree(part, ignore_errors=True)
+    raise RuntimeError(f"bench.py: no writable place for the scene '{args.scene}' among {dirs}: {err}")
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: per-pixel arrays (one row per pixel) as out_dir/<name>.npy
+    in float32, exact for the 8-bit frame and for sample counts below 2^24
+    (float64 above).  Every dumped value is finite: where the render left an
+    infinity or a NaN (the reference's arithmetic does in a few pixels, and the
+    product reproduces it) the value is written as 0 and nonfinite.npy says
+    what stood there: per pixel one base-4 digit per float value, in the order
+    of the arrays and their columns, first value = lowest digit (0 finite,
+    1 +inf, 2 -inf, 3 NaN).  If the arrays would exceed `limit` bytes, every
+    array keeps the same fixed, seeded sample of pixels, whose indices go to
+    pixels.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    n = len(next(iter(arrays.values())))
+    code, digit = np.zeros(n, dtype=np.float64), 1.0
+    for name, a in arrays.items():
+        wide = a.dtype.kind in "iu" and a.size and int(a.max()) >= 1 << 24
+        v = np.array(a, dtype=np.float64 if wide else np.float32)  # (a copy: the caller's array stays as it is)
+        if a.dtype.kind == "f":
+            cols = v.reshape(n, -1)
+            for j in range(cols.shape[1]):
+                c = cols[:, j]
+                code += digit * (1.0 * (c == np.inf) + 2.0 * (c == -np.inf) + 3.0 * np.isnan(c))
+                digit *= 4.0
+            cols[~np.isfinite(cols)] = 0
+        out[name] = v
+    # (the digits of 12 float values fit a float32 exactly, of 26 a float64)
+    out["nonfinite"] = code.astype(np.float32 if digit <= 1 << 24 else np.float64)
+    row_bytes = sum(a.nbytes // n for a in out.values())
+    if n * row_bytes > limit:
+        keep = int((limit - 1024 * (len(out) + 1)) // (row_bytes + 8))  # (room for the .npy headers)
+        pixels = np.sort(np.random.default_rng(20240229).choice(n, size=keep, replace=False))
+        out = {name: a[pixels] for name, a in out.items()}
+        out["pixels"] = pixels.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_info():
@@ -445,6 +541,154 @@ def cpu_baseline(scene_path, W, H, cap_seconds, passes=1):
             "reference_single_core": REF_SINGLE_CORE}
 
 
+def measure_work(rt, args, dscene, gb, host, render_kw, profiles, timed_samples):
+    """--full: the untimed counted calls after the timed region.  Returns the
+    reference-comparable counters of one call, its algorithmic bytes and the
+    dominant kernel's detail (launch times from the timed calls' profiles)."""
+    W, H, P = args.width, args.height, args.passes
+    wavefront = render_kw["kernel"] == rt.KERNEL_WAVEFRONT
+    bounded = wavefront and args.traversal == "bounded"
+    # work counters of one extra (untimed) call -> algorithmic bytes and the
+    # reference deviations (watchdog, longest path, pushes past the 19-entry
+    # stack): the KD traversal, whose counters are the reference's
+    counters = rt.DeviceCounters()
+    copt = rt.options(W, H, P, counters=counters.p, profile=wavefront, **dict(render_kw, traversal=rt.TRAVERSAL_KD))
+    rt.render(dscene, gb, host.camera, 1, copt)
+    c = counters.read(finisher=True)
+    bytes_per_call = algorithmic_bytes(c)
+    if wavefront:
+        launches = sum(p["trace_launches"] for p in profiles)
+        avg_launch_ms = sum(p["trace_ms"] for p in profiles) / max(launches, 1)
+        if bounded:
+            # the dominant kernel (the bounded finisher runs the whole call: one
+            # launch per call) and its own work: one more call of the timed
+            # calls' shape (passes x steps-per-call, the whole-call finisher) with
+            # that finisher counting its own work (RT_TRAVERSAL_BOUNDED_COUNTED:
+            # its COUNT instantiation, one launch)
+            bcnt = rt.DeviceCounters()
+            cp = P * call_steps(args)
+            rt.render(dscene, gb, host.camera, 1, rt.options(W, H, cp, counters=bcnt.p, profile=True,
+                                                             **dict(render_kw, traversal=rt.TRAVERSAL_BOUNDED_COUNTED)))
+            bc = bcnt.read(finisher=True)
+            cprof = rt.last_profile()
+            kname = "wf_finish_bvh<false>"
+            launches = sum(p["finish_launches"] for p in profiles)
+            # per call: the finishers' busy time (the union of their device spans: chained calls'
+            # finishers overlap, and a finisher goes on with the next issued call's pixels) over the
+            # timed calls — the time one launch's worth of work (a call's W x H x passes samples) took
+            busy, hi = 0.0, None
+            for a, b in sorted((p["start_ms"], p["start_ms"] + p["finish_ms"]) for p in profiles):
+                if hi is None or a > hi:
+                    busy += b - a
+                    hi = b
+                elif b > hi:
+                    busy += b - hi
+                    hi = b
+            avg_launch_ms = busy / max(launches, 1)
+            # per launch: the counted bytes per sample x the samples one timed call ran (the timed
+            # region's accumulated samples / its launches: adaptive sampling skips some)
+            samples_per_launch = timed_samples / max(launches, 1)
+            trace_bytes = bounded_kernel_bytes(bc) / max(bc["sample"], 1) * samples_per_launch
+            counted_launches = 1
+            work = {"rays": bc["ray"], "bvh_nodes_per_ray": round(bc["b_bvh_node"] / max(bc["ray"], 1), 2),
+                    "bvh_tests_per_ray": round(bc["b_bvh_tri"] / max(bc["ray"], 1), 2),
+                    "kd_nodes_per_ray": round(bc["node"] / max(bc["ray"], 1), 2),
+                    "kd_tests_per_ray": round(bc["tri"] / max(bc["ray"], 1), 2),
+                    "bary_per_ray": round(bc["b_bary"] / max(bc["ray"], 1), 2),
+                    "rays_per_sample": round(bc["ray"] / max(bc["sample"], 1), 3),
+                    "bytes_per_sample": round(bounded_kernel_bytes(bc) / max(bc["sample"], 1), 1),
+                    "counted_call_passes": cp,
+                    "counted_call_launches": cprof["finish_launches"],
+                    "samples_per_timed_launch": round(samples_per_launch),
+                    "scope": "the finisher's paths; the deep paths handed to wf_long (depth > 64) are not counted"}
+        else:
+            cprof = rt.last_profile()
+            trace_bytes = 8 * (c["node"] - c["finish_node"]) + 40 * (c["tri"] - c["finish_tri"])
+            kname = "wf_trace_coop<false>"
+            counted_launches = cprof["trace_launches"]
+            work = {}
+        bytes_per_launch = trace_bytes / max(counted_launches, 1)
+        kernel_detail = {
+            "kernel": kname,
+            "pipelines": cprof["pipelines"],
+            "launches_per_call": launches / max(len(profiles), 1),
+            "avg_launch_ms": round(avg_launch_ms, 4),
+            "algorithmic_bytes_per_launch": round(bytes_per_launch),
+            "algorithmic_GBps_per_launch": (round(bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9, 1)
+                                            if avg_launch_ms > 0 else None),
+            "trace_union_ms_per_call": round(float(np.mean([p["trace_union_ms"] for p in profiles])), 3),
+            "trace_ms_per_call": round(float(np.mean([p["trace_ms"] for p in profiles])), 3),
+            "shade_ms_per_call": round(float(np.mean([p["shade_ms"] for p in profiles])), 3),
+            "finish_ms_per_call": round(float(np.mean([p["finish_ms"] for p in profiles])), 3),
+            "finisher_spans_ms": [[round(p["start_ms"], 1), round(p["start_ms"] + p["finish_ms"], 1)] for p in profiles]
+            if bounded else None,
+            "call_ms": round(float(np.mean([p["call_ms"] for p in profiles])), 3),
+            "iterations_per_call": round(float(np.mean([p["iterations"] for p in profiles])), 1),
+            "passes_per_call": round(float(np.mean([p["passes"] for p in profiles])), 1),
+        }
+        if work:
+            kernel_detail["kernel_work"] = work
+    else:
+        kernel_detail = {"kernel": "rt_path_kernel<false,20>"}
+    return c, bytes_per_call, kernel_detail
+
+
+def roofline_report(args, pmc, c, bytes_per_call, kernel_detail, total_samples, elapsed):
+    """--full: the line's roofline entry from the counter passes (pmc) and the counted calls."""
+    W, H, P = args.width, args.height, args.passes
+    n = W * H
+    wavefront = args.kernel == "wavefront"
+    samples_per_s = total_samples / elapsed
+    algorithmic_GBps = bytes_per_call / c["sample"] * samples_per_s / 1e9 if c["sample"] else None
+    roof = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None, "traffic": None}
+    if pmc and "error" not in pmc:
+        achieved, detail = roofline_from_pmc(pmc, samples_per_s)
+        roof.update(achieved=round(achieved, 1), frac=round(achieved / HBM_PEAK_GBPS, 4),
+                    traffic=round(detail["hbm_bytes_per_sample"] * n * P), **detail)
+        roof["traffic_unit"] = (f"HBM bytes per step of {P} passes (whole frame, every kernel), from one profiled "
+                                f"call of {P * call_steps(args)} passes = the timed calls' shape")
+        roof["pmc_call_shape"] = ("one UNCHAINED call of the timed calls' passes: counter collection serialises "
+                                  "dispatches, so the chained calls' overlap (a call's deep-path tail beside the "
+                                  "next call's finisher) cannot run under it; the finisher kernel and its per-sample "
+                                  "work are the same, the bytes per sample are applied to the chained timed rate")
+        dk = detail["per_kernel"].get(detail["dominant_kernel"] or "", {})
+        if wavefront and dk.get("dispatches") and kernel_detail["kernel"].split("<")[0] in (detail["dominant_kernel"] or ""):
+            # the dominant kernel alone: its counter bytes per launch / its live
+            # average launch time (HIP events on its pipeline's stream, timed steps)
+            per_launch = 1e9 * (dk.get("fetch_GB", 0.0) + dk.get("write_GB", 0.0)) / dk["dispatches"]
+            kernel_detail["hbm_bytes_per_launch"] = round(per_launch)
+            kernel_detail["hbm_GBps_per_launch"] = round(per_launch / (kernel_detail["avg_launch_ms"] * 1e-3) / 1e9, 1)
+            kernel_detail["hbm_frac_per_launch"] = round(kernel_detail["hbm_GBps_per_launch"] / HBM_PEAK_GBPS, 4)
+    elif pmc:
+        roof["pmc_error"] = pmc["error"]
+        if "settle_s" in pmc:
+            roof["pmc_settle_s"] = pmc["settle_s"]
+    roof.update({
+        "definition": "achieved = counter-measured HBM bytes per sample (FETCH_SIZE x2 + WRITE_SIZE over every "
+                      "dispatch of one profiled call) x timed samples/s; chip-wide, call-level",
+        "algorithmic_GBps": round(algorithmic_GBps, 1) if algorithmic_GBps else None,
+        "algorithmic_bytes_per_sample": round(bytes_per_call / max(c["sample"], 1), 1),
+        "algorithmic_note": "SURVEY §8d bytes the reference's algorithm (the KD traversal) touches; the product's "
+                            "BVH-bounded traversal skips the KD leaves that cannot hold the hit (DESIGN.md §5), so "
+                            "this rate is EXPECTED to exceed the HBM peak: it measures work avoided, not bandwidth",
+        **kernel_detail,
+    })
+    work = kernel_detail.get("kernel_work") or {}
+    if work.get("bytes_per_sample"):
+        # the product's own algorithmic bytes (counted by the kernels in a BOUNDED_COUNTED call of the timed
+        # calls' shape) beside the reference algorithm's: the work ratio, and the product bytes' HBM rate / peak
+        pb = work["bytes_per_sample"]
+        roof["product_bytes_per_sample"] = pb
+        roof["work_ratio"] = round(roof["algorithmic_bytes_per_sample"] / pb, 2)
+        roof["product_GBps"] = round(pb * samples_per_s / 1e9, 1)
+        roof["product_frac"] = round(pb * samples_per_s / 1e9 / HBM_PEAK_GBPS, 4)
+        roof["product_note"] = ("product_bytes_per_sample: per ray 112 B per 4-wide BVH node, 16 B per plane test, 56 B per "
+                                "barycentric record, 8 B per KD node; per hit 176 B of shading records; per sample "
+                                "40 B of pixel state (bench.py bounded_kernel_bytes); frac = the counter-measured "
+                                "HBM traffic / peak, product_frac = these bytes at the timed rate / peak")
+    return roof
+
+
 # ------------------------------------------------------------------ main
 def main(argv=None, binding=None):
     """`binding`: the ctypes binding module (default: isaklm-raytracer_amd/rt.py,
@@ -479,7 +723,7 @@ def main(argv=None, binding=None):
     # counter passes first: the children must own the GPU alone, and this
     # process must not have initialised it yet
     pmc = None
-    if rank == 0 and world == 1 and not args.no_pmc and binding is None:
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and binding is None:
         import rt as rt_host_only
 
         ensure_scene(args, rt_host_only)  # host-only scene generation, once, outside the profiled children
@@ -589,95 +833,22 @@ def main(argv=None, binding=None):
                "max_deep_depth": int(mx.item()), "mismatch_ray": dev.get("mismatch_ray")}
     total_samples = world * n * P * args.steps
     value = total_samples / elapsed / 1e6
-    acc = gb.download()[2]
-    got = int(acc.sum(dtype=np.int64)) if rank == 0 else None
+    final = gb.download()  # the G-buffer as the timed region left it (rank 0: every rank's sum)
+    acc = final[2]
+    if args.dump_outputs and rank == 0:
+        shown = np.zeros((n, 4), dtype=np.uint8)  # the timed region's closing tonemap
+        rt.check(rt.lib().rt_download(ctypes.c_void_p(shown.ctypes.data), rgba, shown.nbytes))
+        dump_outputs(args.dump_outputs, {"frame_buffer": final[0], "squared_luminance": final[1],
+                                         "sample_count": final[2], "rgba": shown})
+    got =int(acc.sum(dtype=np.int64)) if rank == 0 else None
     timed_samples = (int(acc.sum(dtype=np.int64)) - cnt_before) if world == 1 else n * P * args.steps
     # rank 0 after the reduce holds every rank's counts
     actual_samples = got - cnt_before if rank == 0 else None
     expect = world * P * (args.warmup + args.steps)
 
-    # work counters of one extra (untimed) call -> algorithmic bytes and the
-    # reference deviations (watchdog, longest path, pushes past the 19-entry
-    # stack): the KD traversal, whose counters are the reference's
-    counters = rt.DeviceCounters()
-    copt = rt.options(W, H, P, counters=counters.p, profile=wavefront, **dict(render_kw, traversal=rt.TRAVERSAL_KD))
-    rt.render(dscene, gb, host.camera, 1, copt)
-    c = counters.read(finisher=True)
-    bytes_per_call = algorithmic_bytes(c)
-    if wavefront:
-        launches = sum(p["trace_launches"] for p in profiles)
-        avg_launch_ms = sum(p["trace_ms"] for p in profiles) / max(launches, 1)
-        if bounded:
-            # the dominant kernel (the bounded finisher runs the whole call: one
-            # launch per call) and its own work: one more call of the timed
-            # calls' shape (passes x steps-per-call, the whole-call finisher) with
-            # that finisher counting its own work (RT_TRAVERSAL_BOUNDED_COUNTED:
-            # its COUNT instantiation, one launch)
-            bcnt = rt.DeviceCounters()
-            cp = P * call_steps(args)
-            rt.render(dscene, gb, host.camera, 1, rt.options(W, H, cp, counters=bcnt.p, profile=True,
-                                                             **dict(render_kw, traversal=rt.TRAVERSAL_BOUNDED_COUNTED)))
-            bc = bcnt.read(finisher=True)
-            cprof = rt.last_profile()
-            kname = "wf_finish_bvh<false>"
-            launches = sum(p["finish_launches"] for p in profiles)
-            # per call: the finishers' busy time (the union of their device spans: chained calls'
-            # finishers overlap, and a finisher goes on with the next issued call's pixels) over the
-            # timed calls — the time one launch's worth of work (a call's W x H x passes samples) took
-            busy, hi = 0.0, None
-            for a, b in sorted((p["start_ms"], p["start_ms"] + p["finish_ms"]) for p in profiles):
-                if hi is None or a > hi:
-                    busy += b - a
-                    hi = b
-                elif b > hi:
-                    busy += b - hi
-                    hi = b
-            avg_launch_ms = busy / max(launches, 1)
-            # per launch: the counted bytes per sample x the samples one timed call ran (the timed
-            # region's accumulated samples / its launches: adaptive sampling skips some)
-            samples_per_launch = timed_samples / max(launches, 1)
-            trace_bytes = bounded_kernel_bytes(bc) / max(bc["sample"], 1) * samples_per_launch
-            counted_launches = 1
-            work = {"rays": bc["ray"], "bvh_nodes_per_ray": round(bc["b_bvh_node"] / max(bc["ray"], 1), 2),
-                    "bvh_tests_per_ray": round(bc["b_bvh_tri"] / max(bc["ray"], 1), 2),
-                    "kd_nodes_per_ray": round(bc["node"] / max(bc["ray"], 1), 2),
-                    "kd_tests_per_ray": round(bc["tri"] / max(bc["ray"], 1), 2),
-                    "bary_per_ray": round(bc["b_bary"] / max(bc["ray"], 1), 2),
-                    "rays_per_sample": round(bc["ray"] / max(bc["sample"], 1), 3),
-                    "bytes_per_sample": round(bounded_kernel_bytes(bc) / max(bc["sample"], 1), 1),
-                    "counted_call_passes": cp,
-                    "counted_call_launches": cprof["finish_launches"],
-                    "samples_per_timed_launch": round(samples_per_launch),
-                    "scope": "the finisher's paths; the deep paths handed to wf_long (depth > 64) are not counted"}
-        else:
-            cprof = rt.last_profile()
-            trace_bytes = 8 * (c["node"] - c["finish_node"]) + 40 * (c["tri"] - c["finish_tri"])
-            kname = "wf_trace_coop<false>"
-            counted_launches = cprof["trace_launches"]
-            work = {}
-        bytes_per_launch = trace_bytes / max(counted_launches, 1)
-        kernel_detail = {
-            "kernel": kname,
-            "pipelines": cprof["pipelines"],
-            "launches_per_call": launches / max(len(profiles), 1),
-            "avg_launch_ms": round(avg_launch_ms, 4),
-            "algorithmic_bytes_per_launch": round(bytes_per_launch),
-            "algorithmic_GBps_per_launch": (round(bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9, 1)
-                                            if avg_launch_ms > 0 else None),
-            "trace_union_ms_per_call": round(float(np.mean([p["trace_union_ms"] for p in profiles])), 3),
-            "trace_ms_per_call": round(float(np.mean([p["trace_ms"] for p in profiles])), 3),
-            "shade_ms_per_call": round(float(np.mean([p["shade_ms"] for p in profiles])), 3),
-            "finish_ms_per_call": round(float(np.mean([p["finish_ms"] for p in profiles])), 3),
-            "finisher_spans_ms": [[round(p["start_ms"], 1), round(p["start_ms"] + p["finish_ms"], 1)] for p in profiles]
-            if bounded else None,
-            "call_ms": round(float(np.mean([p["call_ms"] for p in profiles])), 3),
-            "iterations_per_call": round(float(np.mean([p["iterations"] for p in profiles])), 1),
-            "passes_per_call": round(float(np.mean([p["passes"] for p in profiles])), 1),
-        }
-        if work:
-            kernel_detail["kernel_work"] = work
-    else:
-        kernel_detail = {"kernel": "rt_path_kernel<false,20>"}
+    c = bytes_per_call = kernel_detail = None
+    if args.full:
+        c, bytes_per_call, kernel_detail = measure_work(rt, args, dscene, gb, host, render_kw, profiles, timed_samples)
 
     if comm:
         comm.close()
@@ -685,54 +856,7 @@ def main(argv=None, binding=None):
         if dist:
             dist.destroy_process_group()
         return 0
-    samples_per_s = total_samples / elapsed
-    algorithmic_GBps = bytes_per_call / c["sample"] * samples_per_s / 1e9 if c["sample"] else None
-    roof = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None, "traffic": None}
-    if pmc and "error" not in pmc:
-        achieved, detail = roofline_from_pmc(pmc, samples_per_s)
-        roof.update(achieved=round(achieved, 1), frac=round(achieved / HBM_PEAK_GBPS, 4),
-                    traffic=round(detail["hbm_bytes_per_sample"] * n * P), **detail)
-        roof["traffic_unit"] = (f"HBM bytes per step of {P} passes (whole frame, every kernel), from one profiled "
-                                f"call of {P * call_steps(args)} passes = the timed calls' shape")
-        roof["pmc_call_shape"] = ("one UNCHAINED call of the timed calls' passes: counter collection serialises "
-                                  "dispatches, so the chained calls' overlap (a call's deep-path tail beside the "
-                                  "next call's finisher) cannot run under it; the finisher kernel and its per-sample "
-                                  "work are the same, the bytes per sample are applied to the chained timed rate")
-        dk = detail["per_kernel"].get(detail["dominant_kernel"] or "", {})
-        if wavefront and dk.get("dispatches") and kernel_detail["kernel"].split("<")[0] in (detail["dominant_kernel"] or ""):
-            # the dominant kernel alone: its counter bytes per launch / its live
-            # average launch time (HIP events on its pipeline's stream, timed steps)
-            per_launch = 1e9 * (dk.get("fetch_GB", 0.0) + dk.get("write_GB", 0.0)) / dk["dispatches"]
-            kernel_detail["hbm_bytes_per_launch"] = round(per_launch)
-            kernel_detail["hbm_GBps_per_launch"] = round(per_launch / (kernel_detail["avg_launch_ms"] * 1e-3) / 1e9, 1)
-            kernel_detail["hbm_frac_per_launch"] = round(kernel_detail["hbm_GBps_per_launch"] / HBM_PEAK_GBPS, 4)
-    elif pmc:
-        roof["pmc_error"] = pmc["error"]
-        if "settle_s" in pmc:
-            roof["pmc_settle_s"] = pmc["settle_s"]
-    roof.update({
-        "definition": "achieved = counter-measured HBM bytes per sample (FETCH_SIZE x2 + WRITE_SIZE over every "
-                      "dispatch of one profiled call) x timed samples/s; chip-wide, call-level",
-        "algorithmic_GBps": round(algorithmic_GBps, 1) if algorithmic_GBps else None,
-        "algorithmic_bytes_per_sample": round(bytes_per_call / max(c["sample"], 1), 1),
-        "algorithmic_note": "SURVEY §8d bytes the reference's algorithm (the KD traversal) touches; the product's "
-                            "BVH-bounded traversal skips the KD leaves that cannot hold the hit (DESIGN.md §5), so "
-                            "this rate is EXPECTED to exceed the HBM peak: it measures work avoided, not bandwidth",
-        **kernel_detail,
-    })
-    work = kernel_detail.get("kernel_work") or {}
-    if work.get("bytes_per_sample"):
-        # the product's own algorithmic bytes (counted by the kernels in a BOUNDED_COUNTED call of the timed
-        # calls' shape) beside the reference algorithm's: the work ratio, and the product bytes' HBM rate / peak
-        pb = work["bytes_per_sample"]
-        roof["product_bytes_per_sample"] = pb
-        roof["work_ratio"] = round(roof["algorithmic_bytes_per_sample"] / pb, 2)
-        roof["product_GBps"] = round(pb * samples_per_s / 1e9, 1)
-        roof["product_frac"] = round(pb * samples_per_s / 1e9 / HBM_PEAK_GBPS, 4)
-        roof["product_note"] = ("product_bytes_per_sample: per ray 112 B per 4-wide BVH node, 16 B per plane test, 56 B per "
-                                "barycentric record, 8 B per KD node; per hit 176 B of shading records; per sample "
-                                "40 B of pixel state (bench.py bounded_kernel_bytes); frac = the counter-measured "
-                                "HBM traffic / peak, product_frac = these bytes at the timed rate / peak")
+    roof = roofline_report(args, pmc, c, bytes_per_call, kernel_detail, total_samples, elapsed) if args.full else None
     line = {
         # BASELINE.json's metric names 1920x1080; another frame size says so
         "metric": METRIC if (W, H) == (1920, 1080) else METRIC.replace("1920×1080", f"{W}×{H}"),
@@ -760,16 +884,18 @@ def main(argv=None, binding=None):
             "parallelism": parallelism,
         },
         "roofline": roof,
-        "per_sample": {k: round(c[k] / max(c["sample"], 1), 3) for k in ("ray", "node", "tri", "hit", "nee")},
+        "full": bool(args.full),  # False: roofline, per_sample, deep_pushes and cpu_baseline are not measured
+        "per_sample": {k: round(c[k] / max(c["sample"], 1), 3) for k in ("ray", "node", "tri", "hit", "nee")} if c else None,
         "deviations": {
             "scope": f"timed region: every path of the {args.steps} timed steps on all ranks "
                      "(always-on statistics of the non-counting bench kernels, rt_deviation_stats)",
             "watchdog_paths": dev["watchdog_paths"], "cut_paths": dev["cut_paths"],
-            "max_path_depth": dev["max_deep_depth"] if dev["deep_paths"] else c["maxdepth"],
+            # (no path deeper than 64 bounces: the counted call's longest path, --full)
+            "max_path_depth": dev["max_deep_depth"] if dev["deep_paths"] else c["maxdepth"] if c else None,
             "deep_paths": dev["deep_paths"],
             "deep_path_hist": {f"{64 << k}-{(64 << (k + 1)) - 1}": h for k, h in enumerate(dev["deep_hist"]) if h},
             "watchdog_limit": 16777215,
-            "deep_pushes": c["deep_push"], "deep_pushes_scope": "one extra counted call of the same options",
+            "deep_pushes": c["deep_push"] if c else None, "deep_pushes_scope": "one extra counted call of the same options",
             "bounded_checked": dev.get("bounded_checked"), "bounded_mismatches": dev.get("bounded_mismatches"),
             "handoff": {k: dev.get(k) for k in getattr(rt, "HANDOFF_FIELDS", ())},
             "handoff_note": "the deep-path hand-off over the timed region: owed_pixels / owed_passes = pixels that "
@@ -789,7 +915,7 @@ def main(argv=None, binding=None):
         "value_actual": round(actual_samples / elapsed / 1e6, 3) if actual_samples is not None else None,
         "setup_s": round(setup_s, 2),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the whole job for the Cornell config, full frame x 1 spp otherwise
         job = P * args.steps if args.scene == "cornell" else 1
         line["cpu_baseline"] = cpu_baseline(scene_file, W, H, args.cpu_seconds, passes=job)

@@ -78,6 +78,96 @@ def test_roofline_from_counters(tmp_path):
     assert d["latency"]["valu_lane_util"] == pytest.approx(4800.0 / (64 * 100.0), abs=1e-3)
 
 
+def test_plain_run_times_its_steps_and_dumps_what_they_left(tmp_path, capsys):
+    """A plain run (no --full) over the CPU stand-in binding: the warm-up and
+    the timed steps are its only renders, the line says what was not
+    measured, and --dump-outputs holds the G-buffer those steps left."""
+    import json
+
+    import numpy as np
+
+    import bench_stub_rt
+    import helpers
+
+    helpers.scene_path("cornell")
+    W, H, P = 12, 8, 2
+    out = tmp_path / "dump"
+    del bench_stub_rt.calls[:]
+    rc = bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--passes", str(P), "--steps-per-call", "2",
+                     "--scene", "cornell", "--width", str(W), "--height", str(H), "--scene-dir", helpers.SCENE_DIR,
+                     "--dump-outputs", str(out)], binding=bench_stub_rt)
+    assert rc == 0
+    line = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+    # (sample_count argument, passes) of every render: 1 warm-up step, then 3 timed steps in calls of 2 + 1
+    assert [c[1:] for c in bench_stub_rt.calls] == [(0, P), (1, 2 * P), (1, P)]
+    assert line["steps"] == 3 and line["full"] is False
+    assert line["roofline"] is None and line["per_sample"] is None and line["cpu_baseline"] is None
+    # (both figures are rounded to 3 decimals on the line)
+    assert line["value"] == pytest.approx(W * H * P * 3 / (line["ms_per_step"] * 3 / 1e3) / 1e6, rel=2e-2, abs=2e-3)
+    ref, _ = helpers.oracle_render(helpers.scene_path("cornell"), W, H, [P, 2 * P, P])
+    got = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(got) == ["frame_buffer", "nonfinite", "rgba", "sample_count", "squared_luminance"]
+    assert not got["nonfinite"].any()  # (Cornell at these sizes: every sum finite, nothing replaced)
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["frame_buffer"], ref[0]) and np.array_equal(got["squared_luminance"], ref[1])
+    assert np.array_equal(got["sample_count"], np.full(W * H, 4 * P, np.float32))
+    assert got["rgba"].shape == (W * H, 4)
+
+
+def test_scene_goes_to_the_user_cache_when_the_scene_dir_cannot_be_written(tmp_path, monkeypatch):
+    """A run from a tree its user cannot write to: the scene is generated once
+    into the user's cache and found there by the next run."""
+    import rt
+
+    blocked = tmp_path / "file"
+    blocked.write_text("")  # a directory below a regular file cannot be made, whoever asks
+    monkeypatch.setenv("XDG_CACHE_HOME", str(tmp_path / "cache"))
+    args = bench.parse_args(["--scene", "cornell", "--scene-dir", str(blocked / "scenes")])
+    first = bench.ensure_scene(args, rt)
+    assert first == str(tmp_path / "cache" / "isaklm-raytracer_amd" / "scenes" / "cornell" / "scene.txt")
+    assert os.path.exists(first) and rt.HostScene(first).triangle_ptr()[1] > 0
+    stamp = os.path.getmtime(first)
+    assert bench.ensure_scene(args, rt) == first and os.path.getmtime(first) == stamp
+    assert os.listdir(tmp_path / "cache" / "isaklm-raytracer_amd" / "scenes") == ["cornell"]
+
+
+def test_dump_outputs_are_finite_and_say_where_the_render_was_not(tmp_path):
+    import numpy as np
+
+    fb = np.arange(12, dtype=np.float32).reshape(4, 3)
+    fb[1] = [np.inf, 5.0, np.nan]
+    fb[3, 1] = -np.inf
+    sq = np.array([1.0, np.nan, 2.0, 3.0], np.float32)
+    kept = fb.copy()
+    bench.dump_outputs(str(tmp_path), {"frame_buffer": fb, "squared_luminance": sq,
+                                       "sample_count": np.full(4, 7, np.int32)})
+    assert np.array_equal(fb, kept, equal_nan=True)  # the caller's arrays are left alone
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(np.isfinite(a).all() and a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["frame_buffer"], [[0, 1, 2], [0, 5, 0], [6, 7, 8], [9, 0, 11]])
+    assert np.array_equal(got["squared_luminance"], [1, 0, 2, 3])
+    # base-4 digits, lowest first: fb.x, fb.y, fb.z, sq; 1 +inf, 2 -inf, 3 NaN
+    assert np.array_equal(got["nonfinite"], [0, 1 + 3 * 16 + 3 * 64, 0, 2 * 4])
+
+
+def test_dump_outputs_samples_the_same_pixels_of_a_large_frame(tmp_path):
+    import numpy as np
+
+    n = 5000
+    arrays = {"frame_buffer": np.arange(3 * n, dtype=np.float32).reshape(n, 3),
+              "sample_count": np.arange(n, dtype=np.int32) + (1 << 24)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=40000)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 40000
+    pix = got["pixels"].astype(np.int64)
+    assert 1000 < len(pix) < n and np.all(np.diff(pix) > 0)
+    assert np.array_equal(got["frame_buffer"], arrays["frame_buffer"][pix])
+    assert got["sample_count"].dtype == np.float64  # counts of 2^24 and more are not exact in float32
+    assert np.array_equal(got["sample_count"], arrays["sample_count"][pix])
+    assert np.array_equal(pix, np.load(tmp_path / "b" / "pixels.npy"))  # the same sample in every run
+
+
 def test_metric_names_the_rendered_frame():
     assert "1920×1080" in bench.METRIC
 

@@ -28,7 +28,8 @@ def test_bench_two_ranks_accounting(tmp_path):
     helpers.scene_path("cornell")  # generated once, before the ranks start
     W, H, P, STEPS, WARM = 24, 16, 2, 3, 1
     argv = ["--gpus", "2", "--steps", str(STEPS), "--warmup", str(WARM), "--passes", str(P), "--steps-per-call", "2",
-            "--scene", "cornell", "--width", str(W), "--height", str(H), "--no-pmc", "--scene-dir", helpers.SCENE_DIR]
+            "--scene", "cornell", "--width", str(W), "--height", str(H), "--full", "--no-pmc",
+            "--scene-dir", helpers.SCENE_DIR]
     port = str(_port())
     procs = []
     for r in range(2):

@@ -3,7 +3,7 @@
 set -e
 OUT=${1:-gpurun_out/configs.jsonl}
 : > $OUT
-run() { timeout -k 10 900 python bench.py "$@" | tail -1 >> $OUT; }
+run() { timeout -k 10 900 python bench.py --full "$@" | tail -1 >> $OUT; }
 # configs[0]: Cornell ~36 tris, 256x256, 64 spp (also the CPU-only case)
 run --scene cornell --width 256 --height 256 --passes 64 --steps 8 --warmup 2 
 # configs[1]: Cornell + ~50k-tri mesh, 1280x720, 256 spp
