@@ -58,11 +58,13 @@ extern "C" {
  * rt_join, rt_shutdown; 7 = RtDeviations' hand-off fields (owed passes,
  * safety-net exits, stranded pixels, dropped guard records, linger
  * expiries), RT_E_INCOMPLETE from the joins, rt_profile_history; 8 =
- * RtDeviations.long_closed, RtOptions.coalesce_passes (both structs grew).
+ * RtDeviations.long_closed, RtOptions.coalesce_passes (both structs grew);
+ * 9 = RtDeviations.wide_overflows (the struct grew), RT_DEBUG_WIDE_CAP1,
+ * RT_DEBUG_COUNT_LONG_ONLY.
  * An integrator checks
  * rt_abi_version() == RT_ABI_VERSION at start-up: a binary built against an
  * older header would otherwise link (C linkage) and mis-pass arguments. */
-#define RT_ABI_VERSION 8
+#define RT_ABI_VERSION 9
 
 /* CUDA uchar4, used for texels (rt/scene.cuh:18) */
 typedef struct RtUChar4 { uint8_t x, y, z, w; } RtUChar4;
@@ -515,6 +517,11 @@ typedef struct RtOptions {
 #define RT_DEBUG_SERIAL_LONG_FIRST 16 /* tests of serialised dispatch (a profiler's counter collection): the
                                        * long-path kernel runs to its end before the path kernel starts */
 #define RT_DEBUG_SERIAL_FIN_FIRST 32  /* ... the path kernel runs to its end before the long-path kernel starts */
+#define RT_DEBUG_WIDE_CAP1 64 /* tests of the long-path kernel's wave-wide bound query: its lists hold one item, so
+                              * every query overflows and the ray is traced the other way (identical results,
+                              * RtDeviations.wide_overflows counts them) */
+#define RT_DEBUG_COUNT_LONG_ONLY 128 /* measurement (RT_TRAVERSAL_BOUNDED_COUNTED calls): only the long-path kernel
+                                     * counts, so the counters hold the deep bounces' work alone */
 /* (calls with RT_DEBUG_CALL_LOG, _LONG_LOG or _SERIAL_* are never coalesced) */
 
 /* Per-call kernel timing of the last rt_render on this device with
@@ -591,6 +598,12 @@ typedef struct RtDeviations {
     unsigned long long check_dropped;
     unsigned long long linger_expiries;
     unsigned long long long_closed;
+    /* wide_overflows (ABI 9): bounces of the long-path kernel whose wave-wide
+     * bound query outgrew its on-chip lists and were traced by the wide KD
+     * traversal instead (identical results, a slower bounce; 0 in the recorded
+     * runs of the 2M-triangle bench scene: the lists are sized on its grazing
+     * rays, csrc/wide_bvh_caps.h). */
+    unsigned long long wide_overflows;
 } RtDeviations;
 int rt_deviation_stats(RtDeviations *out, int reset);
 

@@ -123,6 +123,7 @@ int upload_prepared(const rt_host::PreparedHost &h, int ntris, int nindices, rt_
     RtDevScene &dv = s->dev;
     dv.bvh_nodes = nullptr;
     dv.bvh4 = nullptr;
+    dv.bvh_wide = nullptr;
     dv.bvh_a = nullptr;
     dv.bvh_bary = nullptr;
     dv.bvh_scale = h.bvh_scale;
@@ -134,6 +135,7 @@ int upload_prepared(const rt_host::PreparedHost &h, int ntris, int nindices, rt_
     for (int a = 0; a < 4; ++a) dv.split_off[a] = h.split_off[a];
     if (h.bvh_depth >= 0 && ((rc = upload_vec(*s, h.bvh_nodes, &dv.bvh_nodes)) ||
                              (rc = upload_vec(*s, h.bvh4, &dv.bvh4)) ||
+                             (rc = upload_vec(*s, h.bvh_wide, &dv.bvh_wide)) ||
                              (rc = upload_vec(*s, h.bvh_a, &dv.bvh_a)) ||
                              (rc = upload_vec(*s, h.bvh_bary, &dv.bvh_bary)) ||
                              (rc = upload_vec(*s, h.split_vals, &dv.split_vals)))) {
@@ -157,6 +159,7 @@ int upload_prepared(const rt_host::PreparedHost &h, int ntris, int nindices, rt_
     dv.light_count = h.light_count;
     dv.triangle_count = ntris;
     dv.index_count = nindices;
+    dv.node_count = (int)(h.nodes.size() / 2);
     dv.bmin[0] = h.bounds.min.x; dv.bmin[1] = h.bounds.min.y; dv.bmin[2] = h.bounds.min.z;
     dv.bmax[0] = h.bounds.max.x; dv.bmax[1] = h.bounds.max.y; dv.bmax[2] = h.bounds.max.z;
     s->ntris = ntris;
@@ -254,6 +257,7 @@ int rt_deviation_stats(RtDeviations *out, int reset)
     out->check_dropped = w[RT_DEV_CHK_DROP];
     out->linger_expiries = w[RT_DEV_LINGER_EXP];
     out->long_closed = w[RT_DEV_LONG_CLOSED];
+    out->wide_overflows = w[RT_DEV_WIDE_OVERFLOW];
     if (reset) HIPCHK(hipMemset(d, 0, RT_DEV_WORDS * 8));
     return RT_OK;
 }

@@ -369,15 +369,19 @@ int build_bvh(const Triangle *tris, int ntris, const RtF4 *plane, const RtIsectB
 // node.  Layout per node (8 RtF4, 128 B): lo.x, lo.y, lo.z, hi.x, hi.y, hi.z
 // of children 0..3 (one RtF4 each), then the 4 references, then padding;
 // unused slots hold RT_BVH_EMPTY.
-void collapse_bvh4(const std::vector<RtF4> &bin, std::vector<RtF4> &out4)
+namespace {
+
+struct WideChild {
+    uint32_t ref; // the binary tree's reference (an inner child: its binary node)
+    float lo[3], hi[3];
+};
+
+// the collapse rule for any arity: per wide node its children, and idx[binary node] = its wide node
+void collapse_children(const std::vector<RtF4> &bin, size_t arity, std::vector<std::vector<WideChild>> &wide,
+                       std::vector<int> &idx)
 {
-    out4.clear();
+    typedef WideChild Child;
     const size_t nb = bin.size() / 4;
-    if (nb == 0) return;
-    struct Child {
-        uint32_t ref;
-        float lo[3], hi[3];
-    };
     auto child_of = [&](uint32_t node, int c) {
         const RtF4 *nd = &bin[4 * (size_t)node];
         Child ch;
@@ -391,8 +395,8 @@ void collapse_bvh4(const std::vector<RtF4> &bin, std::vector<RtF4> &out4)
         }
         return ch;
     };
-    std::vector<int> idx(nb, -1);
-    std::vector<std::vector<Child>> wide; // per 4-wide node, its children (binary refs)
+    idx.assign(nb, -1);
+    wide.clear();
     std::vector<uint32_t> order{0};
     idx[0] = 0;
     for (size_t q = 0; q < order.size(); ++q) {
@@ -402,7 +406,7 @@ void collapse_bvh4(const std::vector<RtF4> &bin, std::vector<RtF4> &out4)
             const Child x = child_of(b, c);
             if (x.ref != RT_BVH_EMPTY) ch.push_back(x);
         }
-        while (ch.size() < 4) {
+        while (ch.size() < arity) {
             int pick = -1;
             float area = -1.0f;
             for (size_t k = 0; k < ch.size(); ++k) {
@@ -429,6 +433,18 @@ void collapse_bvh4(const std::vector<RtF4> &bin, std::vector<RtF4> &out4)
             }
         wide.push_back(std::move(ch));
     }
+}
+
+} // namespace
+
+void collapse_bvh4(const std::vector<RtF4> &bin, std::vector<RtF4> &out4)
+{
+    out4.clear();
+    if (bin.size() / 4 == 0) return;
+    typedef WideChild Child;
+    std::vector<int> idx;
+    std::vector<std::vector<Child>> wide; // per 4-wide node, its children (binary refs)
+    collapse_children(bin, 4, wide, idx);
     out4.assign(8 * wide.size(), RtF4{0, 0, 0, 0});
     for (size_t i = 0; i < wide.size(); ++i) {
         float *f = reinterpret_cast<float *>(&out4[8 * i]);
@@ -449,6 +465,33 @@ void collapse_bvh4(const std::vector<RtF4> &bin, std::vector<RtF4> &out4)
             memcpy(&f[4 * 6 + k], &ref, 4);
         }
     }
+}
+
+// The wide collapse (bvh_build.h): collapse_bvh4's rule at `arity`, one 32-B record per child.
+void collapse_bvh_wide(const std::vector<RtF4> &bin, int arity, std::vector<RtF4> &out)
+{
+    out.clear();
+    if (bin.size() / 4 == 0 || arity < 2) return;
+    std::vector<int> idx;
+    std::vector<std::vector<WideChild>> wide;
+    collapse_children(bin, (size_t)arity, wide, idx);
+    // (an unused slot: collapse_bvh4's box at +FLT_MAX, which every ray's slab test culls)
+    RtF4 none1{FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX}, none2{FLT_MAX, FLT_MAX, 0.0f, 0.0f};
+    const uint32_t empty = RT_BVH_EMPTY;
+    memcpy(&none2.z, &empty, 4);
+    out.resize(2 * (size_t)arity * wide.size());
+    for (size_t i = 0; i < wide.size(); ++i)
+        for (size_t k = 0; k < (size_t)arity; ++k) {
+            RtF4 *rec = &out[2 * (i * (size_t)arity + k)];
+            rec[0] = none1;
+            rec[1] = none2;
+            if (k >= wide[i].size()) continue;
+            const WideChild &x = wide[i][k];
+            const uint32_t ref = (x.ref & RT_BVH_LEAF) ? x.ref : (uint32_t)idx[x.ref];
+            rec[0] = RtF4{x.lo[0], x.lo[1], x.lo[2], x.hi[0]};
+            rec[1] = RtF4{x.hi[1], x.hi[2], 0.0f, 0.0f};
+            memcpy(&rec[1].z, &ref, 4);
+        }
 }
 
 } // namespace rt_host

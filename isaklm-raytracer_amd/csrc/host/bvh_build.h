@@ -149,4 +149,13 @@ int build_bvh(const Triangle *tris, int ntris, const RtF4 *plane, const RtIsectB
 // lo.z, hi.x, hi.y, hi.z, references, padding).
 void collapse_bvh4(const std::vector<RtF4> &bin, std::vector<RtF4> &out4);
 
+// the `arity`-wide collapse for the one-ray-per-wave query (wide_bvh.h
+// wide_smin), by the same rule as collapse_bvh4: the same boxes (bit copies)
+// and leaf references as the binary tree.  2 RtF4 per child, `arity` children
+// per node (node n's child c at 2 * (n * arity + c)): {lo.x, lo.y, lo.z, hi.x},
+// {hi.y, hi.z, reference, 0} — a node's child boxes are consecutive 32-B
+// records, one per lane; an unused slot holds RT_BVH_EMPTY and a box no ray
+// enters.
+void collapse_bvh_wide(const std::vector<RtF4> &bin, int arity, std::vector<RtF4> &out);
+
 } // namespace rt_host

@@ -279,6 +279,7 @@ int prepare_host(const Triangle *tris, int ntris, const KD_Tree_Node *nodes, int
     if (brc == RT_OK && bvh.depth < RT_BVH_STACK) {
         out.bvh_nodes = std::move(bvh.nodes);
         collapse_bvh4(out.bvh_nodes, out.bvh4);
+        collapse_bvh_wide(out.bvh_nodes, RT_BVHW_ARITY, out.bvh_wide); // (wf_long's one-ray-per-wave query)
         // the 4-wide query pushes up to 3 entries per level: the deepest stack any root-to-leaf
         // path can build must fit the traversal stack (RT_BVH_STACK), else no bounded traversal
         {

@@ -61,11 +61,13 @@
 #define RT_DEV_STRANDED 32    // pixels found still OUT after a join's drain (wf_verify): an incomplete frame
 #define RT_DEV_LONG_CLOSED 33 // wf_long closed the hand-off ring: its call's finisher had not started (serialised
                               // dispatch); the finisher's lanes ran their deep paths themselves
+#define RT_DEV_WIDE_OVERFLOW 34 // wf_long bounces whose wide s_min query overflowed its frontier (traced by the wide
+                               // KD traversal instead: identical results)
 #define RT_DEV_WORDS 48
 // rt_wavefront_join's return when its hand-off check found stranded pixels (-1: a HIP failure)
 #define RT_WAVEFRONT_INCOMPLETE (-2)
 static_assert(RT_DEV_HIST + RT_DEV_HIST_BINS <= RT_DEV_CHECKED && RT_DEV_MISRAY + 4 <= RT_DEV_OWED_PIXELS &&
-                  RT_DEV_LONG_CLOSED < RT_DEV_WORDS,
+                  RT_DEV_WIDE_OVERFLOW < RT_DEV_WORDS,
               "deviation block");
 
 struct RtDevMaterial {          // 64 B
@@ -104,11 +106,14 @@ struct RtDevScene {
     int light_count;
     int triangle_count;
     int index_count;            // KD leaf entries
+    int node_count;             // KD nodes
     float bmin[3], bmax[3];
     // conservative BVH bounding each ray's first hit (host/bvh_build.h,
     // bvh_trace.h); bvh_nodes == nullptr: none (KD-only traversal)
     const RtF4 *bvh_nodes;      // 4 per node: child boxes {lo0, hi0.x}, {hi0.yz, lo1.xy}, {lo1.z, hi1}, {ref0, ref1, -, -}
     const RtF4 *bvh4;           // its 4-wide collapse, 8 per node: lo.x, lo.y, lo.z, hi.x, hi.y, hi.z of 4 children, refs, -
+    const RtF4 *bvh_wide;       // its RT_BVHW_ARITY-wide collapse for one-ray-per-wave queries (wide_bvh.h), 2 per child:
+                                // {lo.x, lo.y, lo.z, hi.x}, {hi.y, hi.z, ref, -}; nullptr: none
     const RtF4 *bvh_a;          // per BVH leaf slot: plane (as isect_a)
     const RtIsectBary *bvh_bary; // per BVH leaf slot: barycentric-test record (as isect_bary)
     float bvh_scale;            // largest |vertex|_1 (rt_ray_margin)
@@ -128,6 +133,10 @@ struct RtDevScene {
 #define RT_BVH_EMPTY 0xFFFFFFFFu
 #define RT_BVH_LEAF_MAX 8
 #define RT_BVH_STACK 64 // traversal stack entries: trees deeper than this are not used
+#ifndef RT_BVHW_ARITY
+#define RT_BVHW_ARITY 16 // children per node of the wide collapse (host/bvh_build.h collapse_bvh_wide): 4, 8, 16, 32 or 64
+#endif
+static_assert(RT_BVHW_ARITY >= 4 && RT_BVHW_ARITY <= 64 && (RT_BVHW_ARITY & (RT_BVHW_ARITY - 1)) == 0, "RT_BVHW_ARITY");
 
 struct RtDevCamera {            // Camera precomputed once per call (same ops as the reference)
     float R[9];                 // rotation_matrix(yaw, pitch): i, j, k

@@ -59,8 +59,15 @@ static_assert(WF_BLOCK % WF_TBLOCK == 0 && WF_TBLOCK % 64 == 0, "WF_TBLOCK must 
 // (80 VGPRs, ~85 spilled) its waves fit the slots a trace block leaves.
 // Measured (as WF_SHADE_WAVES): 13.16 s at 126 VGPRs, 13.16 at 128 (4
 // waves), 12.87 at 80, 12.86 at 72, 12.92 at 64
+// Whole-call mode (the default render): a wf_long block takes the slot of a
+// finisher block — 4 waves, one per SIMD, beside 3 finisher waves of 128 VGPRs
+// each —, so 128 VGPRs cost it no residency and halve its spills (200 -> 101
+// with the wave-wide bounded bounce): 13.3-14.0 vs 14.4-15.6 us per deep
+// bounce alone (room_small sphere) and 18.0-18.8 vs 20.3-21.5 beside a running
+// finisher (room2m), a lone 256-pass room2m call's last deep sample ending at
+// 888 vs 981 ms (profiles/deep_bounded/).
 #ifndef WF_LONG_WAVES
-#define WF_LONG_WAVES 5
+#define WF_LONG_WAVES 4
 #endif
 #ifndef WF_LONG_PRIO
 // wf_long wave priority: a deep path's bounce chain is the call's critical
@@ -301,6 +308,10 @@ struct WfState {
     uint32_t chk_cap; // records per parity (more are dropped: RT_DEV_CHK_DROP)
     int chk_fault; // (RT_DEBUG_CHECK_FAULT, tests: record a wrong result for every checked ray)
     int debug_quit; // (RT_DEBUG_LONG_QUIT, tests: wf_long leaves at once, as by its safety net)
+    // wf_long's bounded bounces (whole-call mode): the wave-wide s_min query and the wave-run bounded KD
+    // traversal (wide_bvh.h).  0: off (the wide KD traversal), 1: on, 2: on with list capacity 1
+    // (RT_DEBUG_WIDE_CAP1, tests: every query overflows and the ray takes the wide KD traversal)
+    int long_wide;
 };
 
 namespace {
@@ -901,6 +912,7 @@ __global__ void __launch_bounds__(WF_BLOCK) wf_trace_dyn(RtDevScene sc, WfState 
 }
 
 #include "coop_trace.h"
+#include "wide_bvh.h"
 
 // Wave-cooperative trace with dynamic ray fetch (coop_trace.h): lanes whose
 // ray finished take the next queued ray at the next round; descents are
@@ -1984,7 +1996,7 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_FIN_OCC) wf_finish_coop(RtDevScen
 // to this kernel through the hand-off ring; each wave claims the next
 // PUBLISHED entry in order (compare-and-swap on the claim counter, never an
 // entry whose publication is still in flight) and runs that path with every
-// ray traced by all 64 lanes (wide_trace), lane 0 shading.
+// ray traced by all 64 lanes (wide_trace; bounded whole calls: wide_bvh.h), lane 0 shading.
 //
 // Two launch forms:
 //  * whole-call mode (st.fin_live != nullptr): ONE persistent launch per call
@@ -2007,9 +2019,11 @@ template <bool COUNT>
 __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc, RtDevFrame fr, RtDevCamera cam, WfState st,
                                                     int final_slice)
 {
-    __shared__ WideItem s_wide[(WF_BLOCK / 64) * WIDE_CAP];
+    __shared__ __attribute__((aligned(16))) WideItem s_wide[(WF_BLOCK / 64) * WIDE_CAP]; // (also wide_smin's 8-B items)
+    static_assert(WSM_LDS_BYTES <= WIDE_CAP * sizeof(WideItem), "the wide s_min query's lists reuse the wave's frontier");
+    static_assert(WSM_KD_STACK * 8 <= 128 * sizeof(int), "the bounded KD phase's stack reuses the wave's chunk_owner marks");
     __shared__ unsigned long long s_key[(WF_BLOCK / 64) * 4];
-    __shared__ int s_mark[2 * WF_BLOCK]; // 128 per wave: chunk_owner marks + junk slots
+    __shared__ __attribute__((aligned(8))) int s_mark[2 * WF_BLOCK]; // 128 per wave: chunk_owner marks + junk slots
     if (WF_LONG_PRIO > 0) __builtin_amdgcn_s_setprio(WF_LONG_PRIO);
     const int lane = __lane_id();
     const int wave = threadIdx.x >> 6;
@@ -2157,10 +2171,29 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
                 const Vec3D o = rt_v3(__shfl(r.o.x, 0), __shfl(r.o.y, 0), __shfl(r.o.z, 0));
                 const Vec3D d = rt_v3(__shfl(r.d.x, 0), __shfl(r.d.y, 0), __shfl(r.d.z, 0));
                 const float en = __shfl(r.entry, 0), ex = __shfl(r.exit_, 0);
-                // entered at the origin's grid cell (kd_origin_frontier), else from the root
-                const int nf = !COUNT && sc.kd_grid > 0 ? kd_origin_frontier(sc, o, d, en, ex, W) : 0;
-                if (nf > 0) wide_trace_from<COUNT>(sc, o, d, nf, W, lane == 0, hit, bx, by, bz, c);
-                else wide_trace<COUNT>(sc, o, d, en, ex, W, lane == 0, hit, bx, by, bz, c);
+                // bounded (bvh_trace.h trace_bvh, one ray per wave): the wave-wide s_min query, then the
+                // bounded KD traversal run by the whole wave, its nodes fetched 64 at a time and its stack in LDS.  A query that outgrows its lists
+                // is abandoned and counted, and the ray takes the wide KD traversal below, as do rays
+                // the bound does not apply to (rt_bounded_ray)
+                bool traced = false;
+                if (st.long_wide && rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
+                    float s_min = ex;
+                    int tk = -1;
+                    traced = wide_smin<COUNT>(sc, o, d, ex, wsm_lds(W.F, W.key, st.long_wide == 2), s_min, tk, c);
+                    if (traced && s_min < ex) { // (every lane: kd_bounded_wave)
+                        LdsStack1 ks{reinterpret_cast<uint2 *>(W.mark)}; // (128 ints: WSM_KD_STACK entries)
+                        const int tstar = tk >= 0 ? (int)sc.bvh_bary[tk].tri : -1;
+                        hit = kd_bounded_wave<COUNT>(sc, o, d, en, ex, s_min, tstar, bx, by, bz, ks,
+                                                     reinterpret_cast<unsigned long long *>(W.F), c);
+                    }
+                    if (!traced && lane == 0) atomicAdd(fr.dev_stats + RT_DEV_WIDE_OVERFLOW, 1ull);
+                }
+                if (!traced) {
+                    // entered at the origin's grid cell (kd_origin_frontier), else from the root
+                    const int nf = !COUNT && sc.kd_grid > 0 ? kd_origin_frontier(sc, o, d, en, ex, W) : 0;
+                    if (nf > 0) wide_trace_from<COUNT>(sc, o, d, nf, W, lane == 0, hit, bx, by, bz, c);
+                    else wide_trace<COUNT>(sc, o, d, en, ex, W, lane == 0, hit, bx, by, bz, c);
+                }
             }
             want = 0;
             if (lane == 0) {
@@ -2601,6 +2634,7 @@ int ensure(Workspace &w, size_t slots, int grid, int npipes)
         st.chk_cap = 0;
         st.chk_fault = 0;
         st.debug_quit = 0;
+        st.long_wide = 0;
     }
     w.slots = slots;
     w.grid = grid;
@@ -2727,6 +2761,7 @@ int launch_whole_now(Workspace &w, int dev, const RtDevScene &sc, const RtDevFra
     st.chk_ctr = w.chk_ctr + par;
     st.chk_fault = (debug & RT_DEBUG_CHECK_FAULT) ? 1 : 0;
     st.debug_quit = (debug & RT_DEBUG_LONG_QUIT) ? 1 : 0;
+    st.long_wide = sc.bvh_wide ? ((debug & RT_DEBUG_WIDE_CAP1) ? 2 : 1) : 0;
     // debug (RT_DEBUG_LONG_LOG): every deep sample's claim / end time and bounces
     if ((debug & RT_DEBUG_LONG_LOG) && !w.long_log_buf &&
         hipMalloc((void **)&w.long_log_buf, 8 * 4 * 65536) != hipSuccess) {
@@ -2795,15 +2830,18 @@ int launch_whole_now(Workspace &w, int dev, const RtDevScene &sc, const RtDevFra
     const bool fin_first = lp && !long_first && (debug & RT_DEBUG_SERIAL_FIN_FIRST);
     auto launch_long = [&]() -> int {
         if (hipStreamWaitEvent(lp->stream, fin_first ? pp.fin_done : w.fin_ready, 0) != hipSuccess) return -1;
-        hipLaunchKernelGGL(wf_long<false>, dim3(WF_LONG_BLOCKS), dim3(WF_BLOCK), 0, lp->stream, sc, fr, cam, st, 1);
+        // (a counting call: wf_long counts its own work too — its bounded bounces' query rounds, wide nodes and
+        // tests, wide_bvh.h —, so that the device's work per deep bounce can be set against the host model's)
+        if (count) hipLaunchKernelGGL(wf_long<true>, dim3(WF_LONG_BLOCKS), dim3(WF_BLOCK), 0, lp->stream, sc, fr, cam, st, 1);
+        else hipLaunchKernelGGL(wf_long<false>, dim3(WF_LONG_BLOCKS), dim3(WF_BLOCK), 0, lp->stream, sc, fr, cam, st, 1);
         if (hipGetLastError() != hipSuccess) return -1;
         if (hipEventRecord(lp->long_done, lp->stream) != hipSuccess) return -1;
         lp->long_rec = true;
         return 0;
     };
     if (long_first && (launch_long() != 0 || hipStreamWaitEvent(s, lp->long_done, 0) != hipSuccess)) return -1;
-    // Counting: the finisher's own work; wf_long's deep paths are not counted
-    if (count) hipLaunchKernelGGL(wf_finish_bvh<true>, dim3(fgrid), dim3(WF_BLOCK), 0, s, sc, fr, cam, st, 0);
+    // Counting: the finisher's own work and wf_long's (RT_DEBUG_COUNT_LONG_ONLY: wf_long's alone, tools/wide_rounds.py)
+    if (count && !(debug & RT_DEBUG_COUNT_LONG_ONLY)) hipLaunchKernelGGL(wf_finish_bvh<true>, dim3(fgrid), dim3(WF_BLOCK), 0, s, sc, fr, cam, st, 0);
     else if (fgrid <= w.cus * WF_FIN_SMALL_WAVES)
         hipLaunchKernelGGL((wf_finish_bvh<false, 1>), dim3(fgrid), dim3(WF_BLOCK), 0, s, sc, fr, cam, st, 0);
     else hipLaunchKernelGGL(wf_finish_bvh<false>, dim3(fgrid), dim3(WF_BLOCK), 0, s, sc, fr, cam, st, 0);
@@ -2938,6 +2976,7 @@ int launch_drain(Workspace &w)
     st.chk_ctr = w.chk_ctr;
     st.chk_fault = 0;
     st.debug_quit = (w.last_debug & RT_DEBUG_LONG_QUIT) ? 1 : 0;
+    st.long_wide = w.last_sc.bvh_wide ? ((w.last_debug & RT_DEBUG_WIDE_CAP1) ? 2 : 1) : 0;
     st.long_log = nullptr;
     int fgrid = (int)((slots + WF_BLOCK - 1) / WF_BLOCK);
     fgrid = fgrid > w.grid - WF_LONG_BLOCKS ? w.grid - WF_LONG_BLOCKS : fgrid;

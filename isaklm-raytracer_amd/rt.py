@@ -96,11 +96,11 @@ class RtDeviations(ctypes.Structure):
                 ("owed_pixels", ctypes.c_ulonglong), ("owed_passes", ctypes.c_ulonglong),
                 ("long_safety_quits", ctypes.c_ulonglong), ("stranded_pixels", ctypes.c_ulonglong),
                 ("check_dropped", ctypes.c_ulonglong), ("linger_expiries", ctypes.c_ulonglong),
-                ("long_closed", ctypes.c_ulonglong)]
+                ("long_closed", ctypes.c_ulonglong), ("wide_overflows", ctypes.c_ulonglong)]
 
 
 HANDOFF_FIELDS = ("owed_pixels", "owed_passes", "long_safety_quits", "stranded_pixels", "check_dropped",
-                  "linger_expiries", "long_closed")
+                  "linger_expiries", "long_closed", "wide_overflows")
 
 
 def deviation_stats(reset=False):
@@ -126,10 +126,12 @@ def join(stream=None):
     check(lib().rt_join(stream))
 
 
-ABI_VERSION = 8  # RT_ABI_VERSION of include/isaklm_rt.h
+ABI_VERSION = 9  # RT_ABI_VERSION of include/isaklm_rt.h
 E_INCOMPLETE = -7  # RT_E_INCOMPLETE: a join found stranded pixels
 DEBUG_CALL_LOG, DEBUG_LONG_LOG, DEBUG_CHECK_FAULT, DEBUG_LONG_QUIT = 1, 2, 4, 8  # RtOptions.debug bits
 DEBUG_SERIAL_LONG_FIRST, DEBUG_SERIAL_FIN_FIRST = 16, 32  # (tests: serialised dispatch in either order)
+DEBUG_COUNT_LONG_ONLY = 128  # (measurement: a counted call in which only wf_long counts, tools/wide_rounds.py)
+DEBUG_WIDE_CAP1 = 64  # (tests: wf_long's wave-wide s_min query overflows at once; deviation_stats wide_overflows)
 TRIANGLE_BYTES = 152
 NODE_BYTES = 20
 COUNTER_NAMES = ["node", "tri", "hit", "texel", "nee", "sample", "skip", "ray", "watchdog", "maxdepth"]

@@ -4,9 +4,16 @@
 // KD traversal's nodes / leaves / tests, the bounded traversal's BVH nodes /
 // leaf visits and KD nodes, and the s_min query over an 8-wide collapse of the
 // same BVH (node visits, visits that test leaves) — the dependent-load chains
-// a lone ray pays.  Experiment tooling, not product code.
+// a lone ray pays.  Also the model of wf_long's level-synchronous s_min query
+// (csrc/wide_bvh.h wide_smin, restated in csrc/host/wide_smin_host.h) over
+// the wide collapse at a given arity: per ray its dependent rounds (the leaves
+// a round lists are tested in the next one), wide nodes expanded, slots
+// tested, the largest frontier, and the KD nodes the bounded traversal still
+// visits below the start node of the grid cell holding P = o + d * s_min.
+// Both for TIR-like chords (cos to the inward axis 0.2-0.7) and grazing ones
+// (0.02-0.2).  Experiment tooling, not product code.
 //
-// usage: deep_ray_work scene.txt [rays] [seed]
+// usage: deep_ray_work scene.txt [rays] [seed] [arity,arity,...]
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -16,8 +23,7 @@
 #include <random>
 #include <vector>
 
-#include "host/bvh_build.h"
-#include "host/rt_host.h"
+#include "host/wide_smin_host.h"
 
 namespace {
 
@@ -51,15 +57,22 @@ bool box(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float &t1, float &t2)
 }
 
 // KD traversal (rt/trace_ray.cuh:244-318) with the skip bound s_min (-inf: plain)
+// (mark: a node; *below counts the nodes visited from the first visit of `mark` on, -1 if never visited)
 int kd(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float entry, float exit_, float s_min, double &nodes,
-       double &leaves, double &tests)
+       double &leaves, double &tests, uint32_t mark = 0xFFFFFFFFu, double *below = nullptr)
 {
+    const double nodes0 = nodes;
+    if (below) *below = -1;
+    auto seen = [&](uint32_t n) {
+        if (below && *below < 0 && n == mark) *below = -(nodes - nodes0) - 2; // (encoded: visited at this count)
+    };
     struct E { uint32_t n; float e; } stk[64];
     int sp = 0;
     const float root_exit = exit_;
     uint32_t node = 0;
     while (true) {
         uint32_t x = h.nodes[2 * node], y = h.nodes[2 * node + 1];
+        seen(node);
         ++nodes;
         while ((y & 3u) != RT_LEAF_TAG) {
             const uint32_t a = y & 3u;
@@ -73,6 +86,7 @@ int kd(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float entry, float exit
             else { stk[sp++] = E{fc, t}; node = nc; exit_ = t; }
             x = h.nodes[2 * node];
             y = h.nodes[2 * node + 1];
+            seen(node);
             ++nodes;
         }
         const uint32_t cnt = y >> 2;
@@ -85,9 +99,15 @@ int kd(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float entry, float exit
                 ++tests;
                 if (test(h.isect_a.data(), h.isect_bary.data(), e, o, d, sm, s)) { sm = s; best = (int)h.isect_bary[e].tri; }
             }
-            if (best >= 0) return best;
+            if (best >= 0) {
+                if (below && *below < -1) *below = (nodes - nodes0) - (-*below - 2);
+                return best;
+            }
         }
-        if (sp == 0) return -1;
+        if (sp == 0) {
+            if (below && *below < -1) *below = (nodes - nodes0) - (-*below - 2);
+            return -1;
+        }
         --sp;
         node = stk[sp].n;
         entry = stk[sp].e;
@@ -292,9 +312,23 @@ int main(int argc, char **argv)
     }
     for (int k = 0; k < 2; ++k)
         for (int a = 0; a < 3; ++a) c[k][a] /= cn[k] > 0 ? cn[k] : 1;
+    std::vector<int> arities{4, 8, 16, 64};
+    if (argc > 4) {
+        arities.clear();
+        for (char *t = strtok(argv[4], ","); t; t = strtok(nullptr, ",")) arities.push_back(atoi(t));
+    }
+    std::vector<std::vector<RtF4>> wides(arities.size());
+    for (size_t k = 0; k < arities.size(); ++k) rt_host::collapse_bvh_wide(h.bvh_nodes, arities[k], wides[k]);
+    struct Model { double rounds = 0, nodes = 0, tests = 0, n = 0, differ = 0; int rmax = 0, frontier = 0; };
+    std::vector<Model> mdl[2];
+    mdl[0].resize(arities.size());
+    mdl[1].resize(arities.size());
+    double kd_below[2] = {0, 0}, kd_full[2] = {0, 0}, kd_on_path[2] = {0, 0}, kd_rays[2] = {0, 0};
     std::uniform_real_distribution<float> U(0.0f, 1.0f);
     W w;
     long long mism = 0;
+    const float ranges[2][2] = {{0.2f, 0.7f}, {0.02f, 0.2f}};
+    for (int rg = 0; rg < 2; ++rg)
     for (long long r = 0; r < rays; ++r) {
         const Triangle &t = scene.tris[glass[(size_t)(U(rng) * glass.size()) % glass.size()]];
         float b1 = U(rng), b2 = U(rng);
@@ -303,20 +337,57 @@ int main(int argc, char **argv)
         const int k = o.x < xmid ? 0 : 1;
         const Vec3D a = rt_normalize(rt_v3((float)c[k][0] - o.x, (float)c[k][1] - o.y, (float)c[k][2] - o.z));
         Vec3D d;
-        while (true) { // inward at a TIR-like angle: cos to the inward axis in (0.2, 0.7)
+        while (true) { // inward at a TIR-like (or grazing) angle: cos to the inward axis in the range
             Vec3D v = rt_v3(2 * U(rng) - 1, 2 * U(rng) - 1, 2 * U(rng) - 1);
             const float l = rt_dot(v, v);
             if (l < 1e-6f || l > 1.0f) continue;
             v = rt_normalize(v);
+            if (rg == 1) v = rt_normalize(v - rt_dot(v, a) * a + (ranges[1][0] + (ranges[1][1] - ranges[1][0]) * U(rng)) * a);
             const float ca = rt_dot(v, a);
-            if (ca > 0.2f && ca < 0.7f) { d = v; break; }
+            if (ca > ranges[rg][0] && ca < ranges[rg][1]) { d = v; break; }
         }
         float t1, t2;
         if (!box(h, o, d, t1, t2)) continue;
+        double dummy = 0;
+        const float s2 = bvh2(h, o, d, t2, rg == 0 ? w.b_nodes : dummy, rg == 0 ? w.b_leaves : dummy);
+        // the model: the level-synchronous query at every arity, against the depth-first one
+        for (size_t q = 0; q < arities.size(); ++q) {
+            WsmWork ww;
+            float sm;
+            int tk;
+            if (!wide_smin_host(wides[q], arities[q], h, o, d, t2, 1u << 20, 1u << 20, false, sm, tk, ww)) continue;
+            Model &m = mdl[rg][q];
+            m.n += 1;
+            m.rounds += ww.rounds;
+            m.nodes += (double)ww.nodes;
+            m.tests += (double)ww.tests;
+            m.rmax = ww.rounds > m.rmax ? ww.rounds : m.rmax;
+            m.frontier = ww.frontier > m.frontier ? ww.frontier : m.frontier;
+            if (memcmp(&sm, &s2, 4) != 0) m.differ += 1;
+        }
+        // the bounded KD phase, and its part below the start node of P's grid cell
+        if (s2 < t2 && h.kd_grid > 0) {
+            const int G = h.kd_grid;
+            const float P[3] = {o.x + d.x * s2, o.y + d.y * s2, o.z + d.z * s2};
+            const float bmin[3] = {h.bounds.min.x, h.bounds.min.y, h.bounds.min.z};
+            int cc[3];
+            for (int ax = 0; ax < 3; ++ax) {
+                const float f = (P[ax] - bmin[ax]) * h.kd_grid_scale[ax];
+                cc[ax] = f >= 0.0f ? (f < (float)(G - 1) ? (int)f : G - 1) : 0;
+            }
+            const size_t cell = ((size_t)cc[2] * G + cc[1]) * G + cc[0];
+            double nn = 0, ll = 0, tt = 0, below = -1;
+            (void)kd(h, o, d, t1, t2, s2, nn, ll, tt, h.kd_cell[2 * cell], &below);
+            kd_rays[rg] += 1;
+            kd_full[rg] += nn;
+            if (below >= 0) {
+                kd_on_path[rg] += 1;
+                kd_below[rg] += below;
+            }
+        }
+        if (rg == 1) continue; // (the tool's earlier figures: the first range only)
         w.n += 1;
         const int plain = kd(h, o, d, t1, t2, -INFINITY, w.kd_nodes, w.kd_leaves, w.kd_tests);
-        const float s2 = bvh2(h, o, d, t2, w.b_nodes, w.b_leaves);
-        double dummy = 0;
         const float s8 = bvh8(h, N, idx, o, d, t2, w.w_nodes, w.w_leafvis, w.w_tests);
         if (s8 != s2) ++mism;
         const int bounded = s2 < t2 ? kd(h, o, d, t1, t2, s2, w.bk_nodes, w.bk_leaves, dummy) : -1;
@@ -329,5 +400,18 @@ int main(int argc, char **argv)
            w.b_leaves / R, w.bk_nodes / R, w.bk_leaves / R);
     printf("8-wide BVH per ray: node visits %.1f visits with leaf tests %.1f tests %.1f\n", w.w_nodes / R,
            w.w_leafvis / R, w.w_tests / R);
+    for (int rg = 0; rg < 2; ++rg) {
+        printf("level-synchronous s_min query, cos to the inward axis %.2f-%.2f:\n", ranges[rg][0], ranges[rg][1]);
+        for (size_t q = 0; q < arities.size(); ++q) {
+            const Model &m = mdl[rg][q];
+            const double n = m.n > 0 ? m.n : 1;
+            printf("  arity %2d: rounds %.2f (max %d) wide nodes %.1f tests %.1f largest frontier %d; s_min differing "
+                   "from the depth-first query %.0f of %.0f\n", arities[q], m.rounds / n, m.rmax, m.nodes / n,
+                   m.tests / n, m.frontier, m.differ, m.n);
+        }
+        printf("  bounded KD phase: %.1f nodes per ray from the root; P's cell start node on the path for %.0f of %.0f "
+               "rays, %.1f nodes left below it\n", kd_full[rg] / (kd_rays[rg] > 0 ? kd_rays[rg] : 1), kd_on_path[rg],
+               kd_rays[rg], kd_below[rg] / (kd_on_path[rg] > 0 ? kd_on_path[rg] : 1));
+    }
     return 0;
 }
