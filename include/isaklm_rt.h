@@ -60,11 +60,13 @@ extern "C" {
  * expiries), RT_E_INCOMPLETE from the joins, rt_profile_history; 8 =
  * RtDeviations.long_closed, RtOptions.coalesce_passes (both structs grew);
  * 9 = RtDeviations.wide_overflows (the struct grew), RT_DEBUG_WIDE_CAP1,
- * RT_DEBUG_COUNT_LONG_ONLY.
+ * RT_DEBUG_COUNT_LONG_ONLY; 10 = the ray-query API (rt_trace_rays,
+ * rt_camera_rays, rt_render_aov, RtRayHit, RtRaySurface, RtQueryOptions,
+ * RtAovBuffers): an addition only.
  * An integrator checks
  * rt_abi_version() == RT_ABI_VERSION at start-up: a binary built against an
  * older header would otherwise link (C linkage) and mis-pass arguments. */
-#define RT_ABI_VERSION 9
+#define RT_ABI_VERSION 10
 
 /* CUDA uchar4, used for texels (rt/scene.cuh:18) */
 typedef struct RtUChar4 { uint8_t x, y, z, w; } RtUChar4;
@@ -612,6 +614,62 @@ void rt_default_options(RtOptions *opt);
  * (reset_frame; RNG state is kept), then opt->passes passes run, each one
  * sample for every pixel that passes the adaptive test. */
 int rt_render(rt_scene_t scene, G_Buffer g_buffer, Camera camera, int sample_count, const RtOptions *opt);
+
+/* ---------------- ray queries and first-hit AOVs (ABI 10) ----------------
+ * The renderer's closest-hit query for the caller's own rays: trace_ray
+ * (rt/trace_ray.cuh:244-318) on n rays of 6 floats (origin, direction), and
+ * the first-hit feature buffers of a camera (depth, normal, albedo, triangle
+ * id) that denoisers and compositors take beside a low-spp frame.
+ *
+ * For every ray — any 6 floats whatever: directions are NOT normalised (the
+ * reference's trace_ray does not normalise them either), NaN / Inf / zero
+ * directions and far origins included — triangle, the barycentrics,
+ * position, normal and tangent are bit-identical to the reference's
+ * trace_ray, in either traversal mode.  RT_TRAVERSAL_BOUNDED applies the
+ * conservative-BVH bound only where its exactness argument holds: rays with
+ * 0.5 <= max(|d.x|, |d.y|, |d.z|) <= 2 (every unit direction) that do not lie
+ * in a KD split plane; every other ray is traced by the plain KD traversal
+ * (stats [2] counts them).  RT_TRAVERSAL_BOUNDED_COUNTED is taken as
+ * RT_TRAVERSAL_BOUNDED.
+ *
+ * These calls read the prepared scene only: they neither read nor write a
+ * G_Buffer, join no chain and touch no render workspace, so they may run
+ * between chained rt_render calls.  They share one query workspace per
+ * device (released by rt_shutdown): calls on different streams are ordered
+ * among themselves on the device by an event. */
+typedef struct RtRayHit { int32_t triangle; float bx, by, bz; } RtRayHit; /* 16 B; triangle -1 = miss, b* = 0 */
+typedef struct RtRaySurface {          /* 80 B, 16-B aligned */
+    float position[3]; float t;        /* t = magnitude(position - origin), sqrt((dx*dx + dy*dy) + dz*dz); miss: +inf */
+    float normal[3];   float _pad0;    /* shading normal, flipped against the ray as trace_ray does */
+    float tangent[3];  float _pad1;
+    float albedo[3];   float _pad2;    /* material albedo * texel, as the renderer shades it */
+    float emittance[3]; float _pad3;
+} RtRaySurface;                        /* miss: all fields 0 except t */
+typedef struct RtQueryOptions {
+    int traversal;                     /* RT_TRAVERSAL_BOUNDED (default) or RT_TRAVERSAL_KD */
+    void *stream;                      /* hipStream_t; NULL = synchronous on the null stream */
+    unsigned long long *stats_device;  /* optional, 3 u64, adds: [0] rays, [1] hits, [2] rays traced by the
+                                        * plain KD traversal */
+} RtQueryOptions;
+void rt_default_query_options(RtQueryOptions *opt);
+/* rays_device: n x 6 floats (o.xyz d.xyz), 8-B aligned; hits_device: n RtRayHit, 16-B aligned; surface_device:
+ * n RtRaySurface, 16-B aligned, or NULL.  Records at index n and beyond are never written.  n == 0: RT_OK
+ * without a launch; n < 0, n > 2^31 - 1, a null or misaligned pointer: RT_E_INVALID before any GPU call.
+ * opt NULL = the defaults. */
+int rt_trace_rays(rt_scene_t scene, const float *rays_device, long long n, RtRayHit *hits_device,
+                  RtRaySurface *surface_device, const RtQueryOptions *opt);
+/* The pixel-centre rays of a width x height frame: the renderer's camera ray (rt/path_tracing.cuh:381-391)
+ * with both jitter draws 0.5 and no aperture offset — the origin is the camera position bit for bit; no RNG
+ * is consumed.  rays_device: width*height x 6 floats, 8-B aligned; ray y*width + x is pixel (x, y), row 0 =
+ * bottom (the G_Buffer's orientation).  stream NULL = synchronous. */
+int rt_camera_rays(Camera camera, int width, int height, float *rays_device, void *stream);
+/* width*height entries each, pixel y*width + x, row 0 = bottom; any may be NULL.  depth: RtRaySurface.t
+ * (+inf: miss); normal, albedo: 3 floats per pixel (0: miss); triangle: RtRayHit.triangle (-1: miss). */
+typedef struct RtAovBuffers { float *depth; float *normal; float *albedo; int32_t *triangle; } RtAovBuffers;
+/* rt_camera_rays followed by rt_trace_rays with a surface output, bit for bit, in one kernel that stores no
+ * rays. */
+int rt_render_aov(rt_scene_t scene, Camera camera, int width, int height, const RtAovBuffers *buffers,
+                  const RtQueryOptions *opt);
 
 /* draw_frame's colour math (rt/render.cuh:37-59): correct_color(fb/count) ->
  * RGBA8 into a device buffer of width*height*4 bytes, row 0 = bottom. */

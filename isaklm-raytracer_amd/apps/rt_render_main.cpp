@@ -12,7 +12,11 @@
 //                  [--spp N] [--passes P] [--adaptive 0|1] [--min-samples N]
 //                  [--tolerance T] [--max-depth D] [--kernel mega|wavefront]
 //                  [--shard G N] [--device D] [--out PNG] [--quiet]
-//                  [--checkpoint FILE] [--resume FILE]
+//                  [--checkpoint FILE] [--resume FILE] [--aov PREFIX]
+// --aov writes the first-hit feature buffers of the pixel-centre rays
+// (rt_render_aov) before the render loop: PREFIX.albedo.pfm and
+// PREFIX.normal.pfm (PF, 3 floats per pixel) and PREFIX.depth.pfm (Pf; inf =
+// no hit), little-endian, rows bottom to top (the G_Buffer's orientation).
 // --checkpoint writes the G_Buffer + sample count after every rt_render call
 // (rt_gbuffer_save); --resume continues from such a file (rt_gbuffer_load),
 // bit-identical to a render that never stopped.
@@ -24,6 +28,7 @@
 
 #include <chrono>
 #include <string>
+#include <vector>
 
 #include "isaklm_rt.h"
 
@@ -41,14 +46,51 @@ void usage()
             "usage: rt_render [--scene FILE | --generate NAME DIR] [--width W] [--height H] [--spp N]\n"
             "                 [--passes P] [--adaptive 0|1] [--min-samples N] [--tolerance T] [--max-depth D]\n"
             "                 [--kernel mega|wavefront] [--shard G N] [--device D] [--out PNG] [--quiet]\n"
-            "                 [--checkpoint FILE] [--resume FILE]\n");
+            "                 [--checkpoint FILE] [--resume FILE] [--aov PREFIX]\n");
+}
+
+// PFM: "PF" (3 channels) or "Pf" (1), width height, a negative scale = little-endian, rows bottom to top
+bool write_pfm(const std::string &path, const float *data, int width, int height, int channels)
+{
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", width, height);
+    const size_t n = (size_t)width * height * channels;
+    const bool ok = fwrite(data, sizeof(float), n, f) == n;
+    return fclose(f) == 0 && ok;
+}
+
+// --aov: rt_render_aov into device buffers, downloaded and written as PFM files
+int write_aovs(rt_scene_t scene, Camera camera, int width, int height, const std::string &prefix)
+{
+    const size_t n = (size_t)width * height;
+    RtAovBuffers b = {nullptr, nullptr, nullptr, nullptr};
+    if (rt_device_alloc((void **)&b.depth, n * 4) != RT_OK || rt_device_alloc((void **)&b.normal, n * 12) != RT_OK ||
+        rt_device_alloc((void **)&b.albedo, n * 12) != RT_OK)
+        return fail("aov buffers");
+    if (rt_render_aov(scene, camera, width, height, &b, nullptr) != RT_OK) return fail("render_aov");
+    std::vector<float> host(n * 3);
+    const struct { const char *name; const float *dev; int channels; } planes[3] = {
+        {"albedo", b.albedo, 3}, {"normal", b.normal, 3}, {"depth", b.depth, 1}};
+    for (const auto &pl : planes) {
+        if (rt_download(host.data(), pl.dev, n * pl.channels * sizeof(float)) != RT_OK) return fail("aov download");
+        const std::string path = prefix + "." + pl.name + ".pfm";
+        if (!write_pfm(path, host.data(), width, height, pl.channels)) {
+            fprintf(stderr, "rt_render: cannot write %s\n", path.c_str());
+            return 1;
+        }
+    }
+    rt_free(b.depth);
+    rt_free(b.normal);
+    rt_free(b.albedo);
+    return 0;
 }
 
 } // namespace
 
 int main(int argc, char **argv)
 {
-    std::string scene_path, gen_name, gen_dir, out = "render.png", checkpoint, resume;
+    std::string scene_path, gen_name, gen_dir, out = "render.png", checkpoint, resume, aov;
     int width = 1920, height = 1080, spp = 5000, passes = 64, adaptive = 1, min_samples = 100, max_depth = 0;
     int device = 0, shard_id = 0, num_shards = 1, kernel = RT_KERNEL_WAVEFRONT;
     float tolerance = 0.05f;
@@ -79,6 +121,7 @@ int main(int argc, char **argv)
         else if (a == "--quiet") quiet = true;
         else if (a == "--checkpoint") checkpoint = next();
         else if (a == "--resume") resume = next();
+        else if (a == "--aov") aov = next();
         else {
             usage();
             return 2;
@@ -111,6 +154,8 @@ int main(int argc, char **argv)
     if (rt_scene_prepare(&scene, &prepared) != RT_OK) return fail("prepare"); // counts derived from the tree
     rt_host_scene_destroy(host);
     const double setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+
+    if (!aov.empty() && write_aovs(prepared, camera, width, height, aov) != 0) return 1;
 
     RtOptions opt;
     rt_default_options(&opt);

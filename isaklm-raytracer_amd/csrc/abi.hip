@@ -30,6 +30,14 @@ int rt_wavefront_device_init();
 int rt_wavefront_join(void *stream, int consume);
 void rt_wavefront_shutdown();
 void rt_path_shutdown();
+// query.hip
+int rt_launch_trace_rays(const RtDevScene &sc, const float *rays, long long n, void *hits, void *surface, int traversal,
+                         unsigned long long *stats, hipStream_t stream);
+int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width, int height, float *depth,
+                         float *normal, float *albedo, int *triangle, int traversal, unsigned long long *stats,
+                         hipStream_t stream);
+int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *rays, hipStream_t stream);
+void rt_query_shutdown();
 
 static thread_local std::string g_error;
 
@@ -213,6 +221,7 @@ void rt_shutdown(void)
 {
     rt_wavefront_shutdown();
     rt_path_shutdown();
+    rt_query_shutdown();
     std::lock_guard<std::mutex> g(g_dev_mu);
     for (auto &kv : g_dev_stats) {
         if (hipSetDevice(kv.first) == hipSuccess) (void)hipFree(kv.second);
@@ -755,6 +764,20 @@ void rt_default_options(RtOptions *o)
     o->max_depth = 0;
 }
 
+// Camera::rotation() and tanf(FOV / 2) are frame constants (rt/camera.cuh:22-25, :381)
+static RtDevCamera device_camera(const Camera &cam)
+{
+    RtDevCamera dc;
+    RtM3 R = rt_rotation_matrix(cam.yaw, cam.pitch);
+    dc.R[0] = R.i.x; dc.R[1] = R.i.y; dc.R[2] = R.i.z;
+    dc.R[3] = R.j.x; dc.R[4] = R.j.y; dc.R[5] = R.j.z;
+    dc.R[6] = R.k.x; dc.R[7] = R.k.y; dc.R[8] = R.k.z;
+    dc.pos[0] = cam.position.x; dc.pos[1] = cam.position.y; dc.pos[2] = cam.position.z;
+    dc.tan_half_fov = rt_tanf(cam.FOV / 2);
+    dc.aperture = cam.aperture_radius;
+    return dc;
+}
+
 // render (rt/render.cuh:62-76)
 int rt_render(rt_scene_t scene, G_Buffer g, Camera cam, int sample_count, const RtOptions *opt)
 {
@@ -799,15 +822,7 @@ int rt_render(rt_scene_t scene, G_Buffer g, Camera cam, int sample_count, const 
         return RT_E_HIP;
     }
 
-    // Camera::rotation() and tanf(FOV / 2) are frame constants (rt/camera.cuh:22-25, :381)
-    RtDevCamera dc;
-    RtM3 R = rt_rotation_matrix(cam.yaw, cam.pitch);
-    dc.R[0] = R.i.x; dc.R[1] = R.i.y; dc.R[2] = R.i.z;
-    dc.R[3] = R.j.x; dc.R[4] = R.j.y; dc.R[5] = R.j.z;
-    dc.R[6] = R.k.x; dc.R[7] = R.k.y; dc.R[8] = R.k.z;
-    dc.pos[0] = cam.position.x; dc.pos[1] = cam.position.y; dc.pos[2] = cam.position.z;
-    dc.tan_half_fov = rt_tanf(cam.FOV / 2);
-    dc.aperture = cam.aperture_radius;
+    const RtDevCamera dc = device_camera(cam);
 
     hipStream_t stream = (hipStream_t)o.stream;
     if (o.kernel >= RT_KERNEL_WAVEFRONT && o.kernel <= 3) {
@@ -825,6 +840,104 @@ int rt_render(rt_scene_t scene, G_Buffer g, Camera cam, int sample_count, const 
             rt_set_error("rt_render: kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
             return RT_E_HIP;
         }
+    }
+    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
+}
+
+// ---------------- ray queries and first-hit AOVs (query.hip) ----------------
+void rt_default_query_options(RtQueryOptions *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->traversal = RT_TRAVERSAL_BOUNDED;
+}
+
+static bool misaligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+// the checks every query shares, before any GPU call
+static int query_options(const char *who, rt_scene_t scene, const RtQueryOptions *opt, RtQueryOptions *o)
+{
+    if (opt) *o = *opt; else rt_default_query_options(o);
+    if (!scene) { rt_set_error("%s: null scene", who); return RT_E_INVALID; }
+    if (o->traversal != RT_TRAVERSAL_BOUNDED && o->traversal != RT_TRAVERSAL_KD &&
+        o->traversal != RT_TRAVERSAL_BOUNDED_COUNTED) {
+        rt_set_error("%s: traversal %d", who, o->traversal);
+        return RT_E_INVALID;
+    }
+    if (misaligned(o->stats_device, 8)) { rt_set_error("%s: stats_device is not 8-byte aligned", who); return RT_E_INVALID; }
+    if (scene->max_depth > RT_STACK_DEPTH) {
+        rt_set_error("%s: KD tree depth %d beyond the traversal stack (%d)", who, scene->max_depth, RT_STACK_DEPTH);
+        return RT_E_UNSUPPORTED;
+    }
+    return RT_OK;
+}
+
+int rt_trace_rays(rt_scene_t scene, const float *rays, long long n, RtRayHit *hits, RtRaySurface *surface,
+                  const RtQueryOptions *opt)
+{
+    static_assert(sizeof(RtRayHit) == 16 && sizeof(RtRaySurface) == 80, "query records");
+    RtQueryOptions o;
+    if (!rays || !hits) { rt_set_error("rt_trace_rays: null rays or hits"); return RT_E_INVALID; }
+    if (n < 0 || n > (1LL << 31) - 1) { rt_set_error("rt_trace_rays: n = %lld out of [0, 2^31 - 1]", n); return RT_E_INVALID; }
+    if (misaligned(rays, 8) || misaligned(hits, 16) || misaligned(surface, 16)) {
+        rt_set_error("rt_trace_rays: misaligned pointer (rays 8 B, hits and surface 16 B)");
+        return RT_E_INVALID;
+    }
+    const int rc = query_options("rt_trace_rays", scene, opt, &o);
+    if (rc != RT_OK) return rc;
+    if (n == 0) return RT_OK;
+    rt_register_shutdown();
+    hipStream_t stream = (hipStream_t)o.stream;
+    if (rt_launch_trace_rays(scene->dev, rays, n, hits, surface, o.traversal, o.stats_device, stream) != 0) {
+        rt_set_error("rt_trace_rays: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return RT_E_HIP;
+    }
+    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
+}
+
+static int frame_size_ok(const char *who, int width, int height)
+{
+    if (width < 2 || height <= 0 || (long long)width * height > (1LL << 31) - 1) {
+        rt_set_error("%s: bad frame size %d x %d", who, width, height);
+        return RT_E_INVALID;
+    }
+    return RT_OK;
+}
+
+int rt_camera_rays(Camera cam, int width, int height, float *rays, void *stream)
+{
+    if (!rays || misaligned(rays, 8)) { rt_set_error("rt_camera_rays: null or misaligned rays"); return RT_E_INVALID; }
+    const int rc = frame_size_ok("rt_camera_rays", width, height);
+    if (rc != RT_OK) return rc;
+    if (rt_launch_camera_rays(device_camera(cam), width, height, rays, (hipStream_t)stream) != 0) {
+        rt_set_error("rt_camera_rays: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return RT_E_HIP;
+    }
+    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
+}
+
+int rt_render_aov(rt_scene_t scene, Camera cam, int width, int height, const RtAovBuffers *b, const RtQueryOptions *opt)
+{
+    RtQueryOptions o;
+    if (!b) { rt_set_error("rt_render_aov: null buffers"); return RT_E_INVALID; }
+    if (misaligned(b->depth, 4) || misaligned(b->normal, 4) || misaligned(b->albedo, 4) || misaligned(b->triangle, 4)) {
+        rt_set_error("rt_render_aov: misaligned buffer");
+        return RT_E_INVALID;
+    }
+    int rc = frame_size_ok("rt_render_aov", width, height);
+    if (rc != RT_OK) return rc;
+    rc = query_options("rt_render_aov", scene, opt, &o);
+    if (rc != RT_OK) return rc;
+    if (!b->depth && !b->normal && !b->albedo && !b->triangle && !o.stats_device) return RT_OK; // nothing asked for
+    rt_register_shutdown();
+    hipStream_t stream = (hipStream_t)o.stream;
+    if (rt_launch_render_aov(scene->dev, device_camera(cam), width, height, b->depth, b->normal, b->albedo, b->triangle,
+                             o.traversal, o.stats_device, stream) != 0) {
+        rt_set_error("rt_render_aov: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return RT_E_HIP;
     }
     if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
     return RT_OK;

@@ -1,0 +1,347 @@
+// query.hip — the batched ray query (rt_trace_rays), the camera-ray generator
+// (rt_camera_rays) and the first-hit AOV pass (rt_render_aov).
+//
+// The closest-hit query is the renderer's own: trace_ray (rt/trace_ray.cuh:
+// 244-318) as rt_kernels.h trace() restates it, sped up by the conservative
+// BVH bound of bvh_trace.h where that bound is proven — and surface
+// reconstruction is the renderer's shade().  One persistent kernel template
+// over (ray source, sink):
+//
+//   rt_trace_rays   rays from a buffer      -> hit (+ surface) records
+//   rt_render_aov   rays from the camera    -> planar AOV buffers
+//
+// One ray per lane; the lanes of a wave take their next rays together from a
+// global counter (one wave-aggregated atomic per round).  The traversal stack
+// is Stack<RQ_LDS> in LDS with a per-thread HBM spill area.
+//
+// The domain gate.  trace_bvh's bound is argued (bvh_common.h rt_slab) for
+// the rays a renderer makes: unit directions.  rt_slab clamps 1 / d to
+// +-2^60 and argues from "t <= the scene box's exit <= 6 scale", which holds
+// for |d| ~ 1 only: at |d| ~ 2^-58 and below every axis is clamped, the slab
+// distances no longer are the ray's, and boxes holding the hit are culled (a
+// wrong s_min, a wrong hit).  A public query takes any 6 floats, so the bound
+// is applied only to rays with 0.5 <= max(|d.x|, |d.y|, |d.z|) <= 2 (every
+// unit direction: its largest component is >= 1/sqrt(3)) that rt_bounded_ray
+// admits; every other ray runs trace<false>(), the reference's traversal
+// itself.  Either way the result is trace_ray's, bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <mutex>
+
+#include "bvh_trace.h"
+#include "rt_kernels.h"
+
+#define RQ_BLOCK 256
+#ifndef RQ_LDS
+#define RQ_LDS 10 // stack entries in LDS (20 KB per block); deeper ones spill to HBM
+#endif
+#ifndef RQ_WAVES
+#define RQ_WAVES 4 // waves per SIMD = resident blocks per CU
+#endif
+
+using namespace rtk;
+
+namespace {
+
+// camera_ray (rt_kernels.h; rt/path_tracing.cuh:381-391) with both jitter
+// draws 0.5 and no aperture offset: the pixel centre's direction, the camera
+// position itself as the origin.  Draws nothing from the pixel's RNG.
+__device__ __forceinline__ void camera_ray_centre(const RtDevCamera &cam, int half_w, int half_h, int x, int y,
+                                                  Vec3D &ro, Vec3D &rd)
+{
+    const Vec3D dir = rt_normalize(rt_v3(cam.tan_half_fov * ((float)x + 0.5f - (float)half_w) / (float)half_w,
+                                         cam.tan_half_fov * ((float)y + 0.5f - (float)half_h) / (float)half_w, 1.0f));
+    rd = mat_mul(cam.R, dir);
+    ro = rt_v3(cam.pos[0], cam.pos[1], cam.pos[2]);
+}
+
+// ---- ray sources ----
+struct BufferRays { // n x 6 floats (o.xyz d.xyz), 8-B aligned: three 8-B loads, 1,536 contiguous bytes per wave
+    const float2 *rays;
+    __device__ __forceinline__ void load(uint32_t e, Vec3D &o, Vec3D &d) const
+    {
+        const float2 *p = rays + 3 * (size_t)e;
+        const float2 a = p[0], b = p[1], c = p[2];
+        o = rt_v3(a.x, a.y, b.x);
+        d = rt_v3(b.y, c.x, c.y);
+    }
+};
+struct CameraRays { // ray e = the centre of pixel (e % width, e / width), row 0 = bottom
+    RtDevCamera cam;
+    int width, half_w, half_h;
+    __device__ __forceinline__ void load(uint32_t e, Vec3D &o, Vec3D &d) const
+    {
+        camera_ray_centre(cam, half_w, half_h, (int)(e % (uint32_t)width), (int)(e / (uint32_t)width), o, d);
+    }
+};
+
+// ---- sinks ----
+struct SurfaceOut { // RtRaySurface's fields
+    Vec3D position, normal, tangent, albedo, emittance;
+    float t;
+};
+struct RecordSink { // RtRayHit (one 16-B store) and, if asked for, RtRaySurface (five 16-B stores)
+    float4 *hits;
+    float4 *surface;
+    __device__ __forceinline__ bool wants_surface() const { return surface != nullptr; }
+    __device__ __forceinline__ void hit(uint32_t e, int tri, float bx, float by, float bz) const
+    {
+        hits[e] = make_float4(__int_as_float(tri), bx, by, bz);
+    }
+    __device__ __forceinline__ void surf(uint32_t e, int, const SurfaceOut &s) const
+    {
+        float4 *r = surface + 5 * (size_t)e;
+        r[0] = make_float4(s.position.x, s.position.y, s.position.z, s.t);
+        r[1] = make_float4(s.normal.x, s.normal.y, s.normal.z, 0.0f);
+        r[2] = make_float4(s.tangent.x, s.tangent.y, s.tangent.z, 0.0f);
+        r[3] = make_float4(s.albedo.x, s.albedo.y, s.albedo.z, 0.0f);
+        r[4] = make_float4(s.emittance.x, s.emittance.y, s.emittance.z, 0.0f);
+    }
+};
+struct AovSink { // RtAovBuffers: one array per AOV, any may be null
+    float *depth;
+    float *normal;
+    float *albedo;
+    int *triangle;
+    __device__ __forceinline__ bool wants_surface() const { return depth || normal || albedo; }
+    __device__ __forceinline__ void hit(uint32_t e, int tri, float, float, float) const
+    {
+        if (triangle) triangle[e] = tri;
+    }
+    __device__ __forceinline__ void surf(uint32_t e, int, const SurfaceOut &s) const
+    {
+        if (depth) depth[e] = s.t;
+        if (normal) {
+            float *p = normal + 3 * (size_t)e;
+            p[0] = s.normal.x;
+            p[1] = s.normal.y;
+            p[2] = s.normal.z;
+        }
+        if (albedo) {
+            float *p = albedo + 3 * (size_t)e;
+            p[0] = s.albedo.x;
+            p[1] = s.albedo.y;
+            p[2] = s.albedo.z;
+        }
+    }
+};
+
+// whether the bound's argument covers this direction (a NaN component fails the first part)
+__device__ __forceinline__ bool direction_in_domain(Vec3D d)
+{
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    return (ax <= 2.0f && ay <= 2.0f && az <= 2.0f) && (ax >= 0.5f || ay >= 0.5f || az >= 0.5f);
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// one ray's result into the sink: the hit record, and the surface (the renderer's shade()) if asked for
+template <typename SINK>
+__device__ __forceinline__ void store_result(const RtDevScene &sc, const SINK &sink, uint32_t e, Vec3D o, Vec3D d,
+                                             int tri, float bx, float by, float bz)
+{
+    if (tri < 0) bx = by = bz = 0.0f;
+    sink.hit(e, tri, bx, by, bz);
+    if (!sink.wants_surface()) return;
+    SurfaceOut so;
+    if (tri >= 0) {
+        Surface s;
+        Cnt c; // (not counted)
+        shade<false>(sc, tri, bx, by, bz, d, s, c);
+        so.position = s.position;
+        so.normal = s.normal;
+        so.tangent = s.tangent;
+        so.albedo = s.albedo;
+        so.emittance = s.emittance;
+        so.t = rt_magnitude(s.position - o);
+    } else {
+        const Vec3D z = rt_v3(0.0f, 0.0f, 0.0f);
+        so.position = so.normal = so.tangent = so.albedo = so.emittance = z;
+        so.t = INFINITY;
+    }
+    sink.surf(e, tri, so);
+}
+
+// n rays of `src` into `sink`.  kd_only: RT_TRAVERSAL_KD (or a scene without a
+// BVH).  fetch: the launch's ray counter (zeroed before the launch).  stats
+// (optional) adds [0] rays, [1] hits, [2] rays traced by the plain KD traversal.
+template <typename SRC, typename SINK>
+__global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
+    rt_query_kernel(RtDevScene sc, SRC src, SINK sink, uint32_t n, int kd_only, uint32_t *fetch,
+                    unsigned long long *stats, uint2 *spill, int spill_threads)
+{
+    __shared__ uint32_t s_node[RQ_LDS * RQ_BLOCK];
+    __shared__ float s_entry[RQ_LDS * RQ_BLOCK];
+    const int tid = threadIdx.x;
+    const int gtid = blockIdx.x * RQ_BLOCK + tid;
+    Stack<RQ_LDS> stk{s_node + tid, s_entry + tid, RQ_BLOCK, spill + gtid, spill_threads};
+    Cnt c; // (never counted: every traversal below is the COUNT = false build)
+    const int lane = __lane_id();
+    uint32_t n_rays = 0, n_hits = 0, n_kd = 0;
+    while (true) {
+        const unsigned long long m = __ballot(true);
+        const int leader = __ffsll((long long)m) - 1;
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
+        base = __shfl(base, leader);
+        const uint32_t e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (e >= n) break; // (the counter stops below n + the grid's threads <= 2^31 + 2^20: no wrap)
+        Vec3D o, d;
+        src.load(e, o, d);
+        float bx = 0.0f, by = 0.0f, bz = 0.0f;
+        int tri;
+        // the domain gate (see the head of this file)
+        if (!kd_only && direction_in_domain(d) && rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
+            tri = trace_bvh<false>(sc, o, d, bx, by, bz, stk, c);
+        } else {
+            tri = trace<false>(sc, o, d, bx, by, bz, stk, c);
+            ++n_kd;
+        }
+        ++n_rays;
+        if (tri >= 0) ++n_hits;
+        store_result(sc, sink, e, o, d, tri, bx, by, bz);
+    }
+    if (stats) { // (every lane of the wave is here: the loop's exits reconverge)
+        n_rays = wave_sum(n_rays);
+        n_hits = wave_sum(n_hits);
+        n_kd = wave_sum(n_kd);
+        if (lane == 0) {
+            if (n_rays) atomicAdd(stats + 0, (unsigned long long)n_rays);
+            if (n_hits) atomicAdd(stats + 1, (unsigned long long)n_hits);
+            if (n_kd) atomicAdd(stats + 2, (unsigned long long)n_kd);
+        }
+    }
+}
+
+// rt_camera_rays: ray y*W + x = the centre of pixel (x, y), three 8-B stores per lane
+__global__ void __launch_bounds__(RQ_BLOCK) rt_camera_rays_kernel(CameraRays src, float2 *rays, uint32_t n)
+{
+    const uint32_t e = blockIdx.x * RQ_BLOCK + threadIdx.x;
+    if (e >= n) return;
+    Vec3D o, d;
+    src.load(e, o, d);
+    float2 *p = rays + 3 * (size_t)e;
+    p[0] = make_float2(o.x, o.y);
+    p[1] = make_float2(o.z, d.x);
+    p[2] = make_float2(d.y, d.z);
+}
+
+// ---- host side ----
+// One query workspace per device: the launch's ray counter and the stack
+// spill area (indexed by the resident grid's global thread id), so one query
+// kernel at a time may use it.  Launches are ordered on it by an event — each
+// waits on its stream for the previous launch, whatever stream that was on —
+// under the mutex until the launch is enqueued (as the megakernel's spill
+// area, path_kernel.hip).
+struct QueryWorkspace {
+    uint2 *spill = nullptr;
+    size_t spill_threads = 0;
+    uint32_t *fetch = nullptr;
+    hipEvent_t last = nullptr;
+    bool recorded = false;
+    int blocks = 0; // the resident grid: RQ_WAVES blocks per CU
+};
+std::mutex g_query_mu;
+std::map<int, QueryWorkspace> g_query;
+
+// max(RT_STACK_DEPTH, RT_BVH_STACK) entries in all: the KD part needs <= RT_STACK_DEPTH, the BVH part <= RT_BVH_STACK
+constexpr int kSpillDepth = (RT_BVH_STACK > RT_STACK_DEPTH ? RT_BVH_STACK : RT_STACK_DEPTH) - RQ_LDS;
+
+template <typename SRC, typename SINK>
+int launch_query(const RtDevScene &sc, const SRC &src, const SINK &sink, long long n, int traversal,
+                 unsigned long long *stats, hipStream_t stream)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    std::lock_guard<std::mutex> g(g_query_mu);
+    QueryWorkspace &w = g_query[dev];
+    if (!w.blocks) {
+        hipDeviceProp_t prop;
+        const int cus = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0
+                            ? prop.multiProcessorCount
+                            : 256;
+        w.blocks = cus * RQ_WAVES;
+    }
+    if (!w.last && hipEventCreateWithFlags(&w.last, hipEventDisableTiming) != hipSuccess) return -1;
+    if (!w.fetch) {
+        void *p = nullptr;
+        if (hipMalloc(&p, 64) != hipSuccess) return -1;
+        w.fetch = (uint32_t *)p;
+    }
+    const size_t threads = (size_t)w.blocks * RQ_BLOCK;
+    if (!w.spill) {
+        void *p = nullptr;
+        if (hipMalloc(&p, threads * (size_t)kSpillDepth * sizeof(uint2)) != hipSuccess) return -1;
+        w.spill = (uint2 *)p;
+        w.spill_threads = threads;
+    }
+    if (w.recorded && hipStreamWaitEvent(stream, w.last, 0) != hipSuccess) return -1;
+    if (hipMemsetAsync(w.fetch, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
+    const long long need = (n + RQ_BLOCK - 1) / RQ_BLOCK;
+    const int grid = (int)(need < (long long)w.blocks ? need : (long long)w.blocks);
+    const int kd_only = traversal == RT_TRAVERSAL_KD || sc.bvh_nodes == nullptr || sc.bvh4 == nullptr;
+    hipLaunchKernelGGL((rt_query_kernel<SRC, SINK>), dim3(grid), dim3(RQ_BLOCK), 0, stream, sc, src, sink, (uint32_t)n,
+                       kd_only, w.fetch, stats, w.spill, (int)w.spill_threads);
+    if (hipGetLastError() != hipSuccess || hipEventRecord(w.last, stream) != hipSuccess) return -1;
+    w.recorded = true;
+    return 0;
+}
+
+CameraRays camera_source(const RtDevCamera &cam, int width, int height)
+{
+    CameraRays s;
+    s.cam = cam;
+    s.width = width;
+    s.half_w = width / 2; // SCREEN_W / 2 (integer division), as rt_render's frame
+    s.half_h = height / 2;
+    return s;
+}
+
+} // namespace
+
+// ---- launchers (called by abi.hip) ----
+int rt_launch_trace_rays(const RtDevScene &sc, const float *rays, long long n, void *hits, void *surface, int traversal,
+                         unsigned long long *stats, hipStream_t stream)
+{
+    const BufferRays src{reinterpret_cast<const float2 *>(rays)};
+    const RecordSink sink{reinterpret_cast<float4 *>(hits), reinterpret_cast<float4 *>(surface)};
+    return launch_query(sc, src, sink, n, traversal, stats, stream);
+}
+
+int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width, int height, float *depth,
+                         float *normal, float *albedo, int *triangle, int traversal, unsigned long long *stats,
+                         hipStream_t stream)
+{
+    const AovSink sink{depth, normal, albedo, triangle};
+    return launch_query(sc, camera_source(cam, width, height), sink, (long long)width * height, traversal, stats,
+                        stream);
+}
+
+int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *rays, hipStream_t stream)
+{
+    const uint32_t n = (uint32_t)((long long)width * height);
+    hipLaunchKernelGGL(rt_camera_rays_kernel, dim3((n + RQ_BLOCK - 1) / RQ_BLOCK), dim3(RQ_BLOCK), 0, stream,
+                       camera_source(cam, width, height), reinterpret_cast<float2 *>(rays), n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+void rt_query_shutdown()
+{
+    std::lock_guard<std::mutex> g(g_query_mu);
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    for (auto &kv : g_query) {
+        if (hipSetDevice(kv.first) != hipSuccess) continue;
+        if (kv.second.recorded) (void)hipEventSynchronize(kv.second.last);
+        if (kv.second.spill) (void)hipFree(kv.second.spill);
+        if (kv.second.fetch) (void)hipFree(kv.second.fetch);
+        if (kv.second.last) (void)hipEventDestroy(kv.second.last);
+    }
+    g_query.clear();
+    (void)hipSetDevice(cur);
+}

@@ -67,6 +67,24 @@ class RtProfile(ctypes.Structure):
                 ("trace_union_ms", ctypes.c_float), ("pipelines", ctypes.c_int)]
 
 
+class RtQueryOptions(ctypes.Structure):
+    _fields_ = [("traversal", ctypes.c_int), ("stream", ctypes.c_void_p), ("stats_device", ctypes.c_void_p)]
+
+
+class RtAovBuffers(ctypes.Structure):
+    _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
+                ("triangle", ctypes.c_void_p)]
+
+
+# RtRayHit (16 B) and RtRaySurface (80 B) as numpy record types
+RAY_HIT = np.dtype([("triangle", np.int32), ("bx", np.float32), ("by", np.float32), ("bz", np.float32)])
+RAY_SURFACE = np.dtype([("position", np.float32, 3), ("t", np.float32), ("normal", np.float32, 3),
+                        ("_pad0", np.float32), ("tangent", np.float32, 3), ("_pad1", np.float32),
+                        ("albedo", np.float32, 3), ("_pad2", np.float32), ("emittance", np.float32, 3),
+                        ("_pad3", np.float32)])
+QUERY_STATS = ("rays", "hits", "kd_rays")  # RtQueryOptions.stats_device [0..2]
+
+
 def last_profile():
     """Kernel timing of the last rt_render with options(profile=True) on this device."""
     p = RtProfile()
@@ -126,7 +144,7 @@ def join(stream=None):
     check(lib().rt_join(stream))
 
 
-ABI_VERSION = 9  # RT_ABI_VERSION of include/isaklm_rt.h
+ABI_VERSION = 10  # RT_ABI_VERSION of include/isaklm_rt.h
 E_INCOMPLETE = -7  # RT_E_INCOMPLETE: a join found stranded pixels
 DEBUG_CALL_LOG, DEBUG_LONG_LOG, DEBUG_CHECK_FAULT, DEBUG_LONG_QUIT = 1, 2, 4, 8  # RtOptions.debug bits
 DEBUG_SERIAL_LONG_FIRST, DEBUG_SERIAL_FIN_FIRST = 16, 32  # (tests: serialised dispatch in either order)
@@ -198,6 +216,11 @@ def lib():
         L.rt_deviation_stats.argtypes = [ctypes.POINTER(RtDeviations), i]
         L.rt_join.argtypes = [vp]
         L.rt_profile_history.argtypes = [ctypes.POINTER(RtProfile), i, ctypes.POINTER(i), i]
+        L.rt_default_query_options.argtypes = [ctypes.POINTER(RtQueryOptions)]
+        L.rt_default_query_options.restype = None
+        L.rt_trace_rays.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, ctypes.POINTER(RtQueryOptions)]
+        L.rt_camera_rays.argtypes = [Camera, i, i, vp, vp]
+        L.rt_render_aov.argtypes = [vp, Camera, i, i, ctypes.POINTER(RtAovBuffers), ctypes.POINTER(RtQueryOptions)]
         L.rt_shutdown.restype = None
         L.rt_abi_version.restype = i
         if L.rt_abi_version() != ABI_VERSION:
@@ -430,6 +453,115 @@ def options(width, height, passes=1, adaptive=True, min_samples=100, tolerance=0
 def render(dscene, gbuf, camera, sample_count, opt):
     """render() (rt/render.cuh:62): resets when sample_count == 0, then opt.passes passes."""
     check(lib().rt_render(dscene.prepared, gbuf.g, camera, sample_count, ctypes.byref(opt)))
+
+
+# ---------------------------------------------------------------- ray queries
+def query_options(traversal=None, stream=None, stats=None):
+    """RtQueryOptions; traversal: TRAVERSAL_BOUNDED (the default) / TRAVERSAL_KD; stream: a hipStream_t as an
+    integer (None: synchronous); stats: a device pointer to 3 u64 (rays, hits, rays traced by the plain KD
+    traversal; the call adds to them)."""
+    o = RtQueryOptions()
+    lib().rt_default_query_options(ctypes.byref(o))
+    if traversal is not None:
+        o.traversal = traversal
+    o.stream = stream
+    o.stats_device = stats
+    return o
+
+
+class _DeviceBytes:
+    """a device allocation of the C-ABI, freed on exit"""
+
+    def __init__(self, nbytes):
+        self.p = ctypes.c_void_p()
+        check(lib().rt_device_alloc(ctypes.byref(self.p), max(int(nbytes), 16)))
+
+    def __enter__(self):
+        return self.p
+
+    def __exit__(self, *exc):
+        lib().rt_free(self.p)
+        return False
+
+
+def _int_ptr(p):
+    return p.value if isinstance(p, ctypes.c_void_p) else p
+
+
+def trace_rays_device(dscene, rays_ptr, n, hits_ptr, surface_ptr=None, traversal=None, stream=None, stats_ptr=None):
+    """rt_trace_rays on device memory: integer device pointers (a torch tensor's data_ptr()) to n x 6 float32
+    rays, n RtRayHit (RAY_HIT, 16 B) and optionally n RtRaySurface (RAY_SURFACE, 80 B); stream: an integer
+    hipStream_t (torch.cuda.current_stream().cuda_stream) — the call is then only enqueued."""
+    o = query_options(traversal, stream, _int_ptr(stats_ptr))
+    check(lib().rt_trace_rays(dscene.prepared, _int_ptr(rays_ptr), int(n), _int_ptr(hits_ptr), _int_ptr(surface_ptr),
+                              ctypes.byref(o)))
+
+
+def _synchronize_stream(stream):
+    """the numpy path reads the results back at once: wait for the whole device (the downloads that follow
+    join the renders anyway, as every rt_download does)"""
+    if stream:
+        check(lib().rt_synchronize())
+
+
+def trace_rays(dscene, rays, surface=False, traversal=None, stream=None, stats=False):
+    """Closest hits of `rays` — a numpy (n, 6) float32 array (origin, direction; directions are used as given,
+    not normalised) — bit-identical to the reference's trace_ray.  Returns the RAY_HIT record array
+    (triangle -1: miss); with surface=True also the RAY_SURFACE records; with stats=True also a dict of the
+    call's counts (QUERY_STATS)."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must have shape (n, 6)")
+    n = len(rays)
+    L = lib()
+    hits = np.zeros(n, dtype=RAY_HIT)
+    surf = np.zeros(n, dtype=RAY_SURFACE) if surface else None
+    st = np.zeros(3, dtype=np.uint64)
+    with _DeviceBytes(rays.nbytes) as d_rays, _DeviceBytes(hits.nbytes) as d_hits, \
+            _DeviceBytes(surf.nbytes if surface else 0) as d_surf, _DeviceBytes(st.nbytes) as d_st:
+        if n:
+            check(L.rt_upload(d_rays, _ptr(rays), rays.nbytes))
+        if stats:
+            check(L.rt_memset(d_st, 0, st.nbytes))
+        trace_rays_device(dscene, d_rays, n, d_hits, d_surf if surface else None, traversal, stream,
+                          d_st if stats else None)
+        _synchronize_stream(stream)
+        if n:
+            check(L.rt_download(_ptr(hits), d_hits, hits.nbytes))
+            if surface:
+                check(L.rt_download(_ptr(surf), d_surf, surf.nbytes))
+        if stats:
+            check(L.rt_download(_ptr(st), d_st, st.nbytes))
+    out = (hits,) + ((surf,) if surface else ()) + ((dict(zip(QUERY_STATS, (int(v) for v in st))),) if stats else ())
+    return out[0] if len(out) == 1 else out
+
+
+def camera_rays(camera, width, height):
+    """rt_camera_rays: the (width*height, 6) float32 pixel-centre rays of `camera` (ray y*width + x, row 0 =
+    bottom): the renderer's camera ray with both jitter draws 0.5 and no aperture offset."""
+    rays = np.zeros((width * height, 6), dtype=np.float32)
+    with _DeviceBytes(rays.nbytes) as d:
+        check(lib().rt_camera_rays(camera, width, height, d, None))
+        check(lib().rt_download(_ptr(rays), d, rays.nbytes))
+    return rays
+
+
+def render_aov(dscene, camera, width, height, traversal=None):
+    """rt_render_aov: the first-hit feature buffers of the pixel-centre rays, as a dict of numpy arrays with
+    row 0 = bottom: depth (H, W) float32 (inf: miss), normal and albedo (H, W, 3) float32, triangle (H, W)
+    int32 (-1: miss)."""
+    n = width * height
+    out = {"depth": np.zeros((height, width), np.float32), "normal": np.zeros((height, width, 3), np.float32),
+           "albedo": np.zeros((height, width, 3), np.float32), "triangle": np.zeros((height, width), np.int32)}
+    L = lib()
+    with _DeviceBytes(n * 4) as d_depth, _DeviceBytes(n * 12) as d_normal, _DeviceBytes(n * 12) as d_albedo, \
+            _DeviceBytes(n * 4) as d_tri:
+        b = RtAovBuffers(d_depth, d_normal, d_albedo, d_tri)
+        o = query_options(traversal)
+        check(L.rt_render_aov(dscene.prepared, camera, width, height, ctypes.byref(b), ctypes.byref(o)))
+        for name, d in (("depth", d_depth), ("normal", d_normal), ("albedo", d_albedo), ("triangle", d_tri)):
+            check(L.rt_download(_ptr(out[name]), d, out[name].nbytes))
+    return out
 
 
 class DeviceCounters:
