@@ -62,11 +62,13 @@ extern "C" {
  * 9 = RtDeviations.wide_overflows (the struct grew), RT_DEBUG_WIDE_CAP1,
  * RT_DEBUG_COUNT_LONG_ONLY; 10 = the ray-query API (rt_trace_rays,
  * rt_camera_rays, rt_render_aov, RtRayHit, RtRaySurface, RtQueryOptions,
- * RtAovBuffers): an addition only.
+ * RtAovBuffers): an addition only; 11 = the denoiser (rt_denoise,
+ * rt_denoise_host, rt_default_denoise_options, RtDenoiseOptions) and
+ * rt_tonemap_rgb: additions only.
  * An integrator checks
  * rt_abi_version() == RT_ABI_VERSION at start-up: a binary built against an
  * older header would otherwise link (C linkage) and mis-pass arguments. */
-#define RT_ABI_VERSION 10
+#define RT_ABI_VERSION 11
 
 /* CUDA uchar4, used for texels (rt/scene.cuh:18) */
 typedef struct RtUChar4 { uint8_t x, y, z, w; } RtUChar4;
@@ -679,6 +681,49 @@ int rt_save_render(G_Buffer g_buffer, int width, int height, const char *png_pat
 /* the PNG encoder rt_save_render uses (replaces lodepng::encode,
  * rt/save_render.cuh:18-23): host RGBA8 rows top to bottom */
 int rt_write_png(const char *png_path, const uint8_t *rgba_host, int width, int height);
+
+/* ---------------- denoising (ABI 11) ----------------
+ * A variance-guided edge-avoiding a-trous filter for low-spp frames: the
+ * G_Buffer's mean radiance (frame_buffer / sample_count), smoothed over
+ * `iterations` levels of a 5x5 B3-spline kernel with tap spacing 1, 2, 4, ...,
+ * each tap weighted by edge stops on the first-hit normal and depth
+ * (rt_render_aov's buffers) and on the luminance difference measured in
+ * standard deviations of the pixel's mean (from squared_luminance, the
+ * quantity the adaptive test uses).  Hits and misses never mix.  With
+ * demodulation the filter runs on colour / albedo and the albedo is multiplied
+ * back, so textures stay sharp.  DESIGN.md "Denoising" defines every operation:
+ * all of them are correctly rounded float32 operations in a fixed order, and
+ * rt_denoise (GPU) and rt_denoise_host (CPU) give the same bits.
+ *
+ * rt_denoise reads the frame: like rt_tonemap it first joins the renders
+ * (chained calls' deep-path tails included) on `stream`.  It writes only
+ * rgb_out_device.  It keeps one workspace per device (52 B per pixel of the
+ * last frame, released by rt_shutdown); calls on different streams are
+ * ordered on it by an event.  Errors before any GPU call (RT_E_INVALID): a
+ * null required buffer, a bad size (width or height < 1, width * height >
+ * 2^31 - 1), iterations or normal_log2 out of range, demodulate outside
+ * {-1, 0, 1}, a negative or non-finite sigma. */
+typedef struct RtDenoiseOptions {
+    int   iterations;    /* a-trous levels, tap spacing 1,2,4,...; 0 = default 5; 1..8 */
+    float sigma_lum;     /* 0 = default 4:   luminance edge stop, in standard deviations of the pixel's mean */
+    float sigma_depth;   /* 0 = default 1:   depth edge stop, in local depth slopes */
+    int   normal_log2;   /* 0 = default 7:   normal weight = max(0, n_p.n_q)^(2^k), by k squarings; 1..10 */
+    int   demodulate;    /* 0 = default on (1): filter colour / albedo and multiply back; -1 = off */
+    void *stream;        /* hipStream_t; NULL = synchronous */
+} RtDenoiseOptions;
+void rt_default_denoise_options(RtDenoiseOptions *opt);
+/* rgb_out_device: width*height x 3 floats, mean radiance, row 0 = bottom (the G_Buffer's orientation).
+ * aov: depth and normal required; albedo required unless demodulate = -1; triangle unused.
+ * opt NULL = the defaults. */
+int rt_denoise(G_Buffer g, const RtAovBuffers *aov, int width, int height, float *rgb_out_device,
+               const RtDenoiseOptions *opt);
+/* the same arithmetic on host arrays, same layouts (CPU tier, integrators without a GPU at hand);
+ * opt->stream is ignored */
+int rt_denoise_host(const float *fb, const float *sq, const int *count, const float *depth, const float *normal,
+                    const float *albedo, int width, int height, float *rgb_out, const RtDenoiseOptions *opt);
+/* rt_tonemap's colour math (correct_color -> RGBA8) for a float RGB mean-radiance buffer (width*height x 3
+ * floats, e.g. rt_denoise's output) */
+int rt_tonemap_rgb(const float *rgb_device, uint8_t *rgba_device, int width, int height, void *stream);
 
 /* ---------------- multi-GPU shards ----------------
  * One process per GPU.  Rank 0 makes an id (rt_comm_unique_id), ships its

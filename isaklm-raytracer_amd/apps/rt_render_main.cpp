@@ -12,11 +12,14 @@
 //                  [--spp N] [--passes P] [--adaptive 0|1] [--min-samples N]
 //                  [--tolerance T] [--max-depth D] [--kernel mega|wavefront]
 //                  [--shard G N] [--device D] [--out PNG] [--quiet]
-//                  [--checkpoint FILE] [--resume FILE] [--aov PREFIX]
+//                  [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]
 // --aov writes the first-hit feature buffers of the pixel-centre rays
 // (rt_render_aov) before the render loop: PREFIX.albedo.pfm and
 // PREFIX.normal.pfm (PF, 3 floats per pixel) and PREFIX.depth.pfm (Pf; inf =
 // no hit), little-endian, rows bottom to top (the G_Buffer's orientation).
+// --denoise writes, beside the unchanged --out image, <out stem>.denoised.png:
+// the frame through rt_denoise (guided by the same first-hit buffers; --aov's
+// are reused) and rt_tonemap_rgb, flipped as save_render flips.
 // --checkpoint writes the G_Buffer + sample count after every rt_render call
 // (rt_gbuffer_save); --resume continues from such a file (rt_gbuffer_load),
 // bit-identical to a render that never stopped.
@@ -46,7 +49,7 @@ void usage()
             "usage: rt_render [--scene FILE | --generate NAME DIR] [--width W] [--height H] [--spp N]\n"
             "                 [--passes P] [--adaptive 0|1] [--min-samples N] [--tolerance T] [--max-depth D]\n"
             "                 [--kernel mega|wavefront] [--shard G N] [--device D] [--out PNG] [--quiet]\n"
-            "                 [--checkpoint FILE] [--resume FILE] [--aov PREFIX]\n");
+            "                 [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]\n");
 }
 
 // PFM: "PF" (3 channels) or "Pf" (1), width height, a negative scale = little-endian, rows bottom to top
@@ -60,15 +63,29 @@ bool write_pfm(const std::string &path, const float *data, int width, int height
     return fclose(f) == 0 && ok;
 }
 
-// --aov: rt_render_aov into device buffers, downloaded and written as PFM files
-int write_aovs(rt_scene_t scene, Camera camera, int width, int height, const std::string &prefix)
+// the first-hit feature buffers of the pixel-centre rays (rt_render_aov) in device memory
+int render_aovs(rt_scene_t scene, Camera camera, int width, int height, RtAovBuffers *b)
 {
     const size_t n = (size_t)width * height;
-    RtAovBuffers b = {nullptr, nullptr, nullptr, nullptr};
-    if (rt_device_alloc((void **)&b.depth, n * 4) != RT_OK || rt_device_alloc((void **)&b.normal, n * 12) != RT_OK ||
-        rt_device_alloc((void **)&b.albedo, n * 12) != RT_OK)
+    if (rt_device_alloc((void **)&b->depth, n * 4) != RT_OK || rt_device_alloc((void **)&b->normal, n * 12) != RT_OK ||
+        rt_device_alloc((void **)&b->albedo, n * 12) != RT_OK)
         return fail("aov buffers");
-    if (rt_render_aov(scene, camera, width, height, &b, nullptr) != RT_OK) return fail("render_aov");
+    if (rt_render_aov(scene, camera, width, height, b, nullptr) != RT_OK) return fail("render_aov");
+    return 0;
+}
+
+void free_aovs(RtAovBuffers *b)
+{
+    if (b->depth) rt_free(b->depth);
+    if (b->normal) rt_free(b->normal);
+    if (b->albedo) rt_free(b->albedo);
+    b->depth = b->normal = b->albedo = nullptr;
+}
+
+// --aov: the buffers downloaded and written as PFM files
+int write_aovs(const RtAovBuffers &b, int width, int height, const std::string &prefix)
+{
+    const size_t n = (size_t)width * height;
     std::vector<float> host(n * 3);
     const struct { const char *name; const float *dev; int channels; } planes[3] = {
         {"albedo", b.albedo, 3}, {"normal", b.normal, 3}, {"depth", b.depth, 1}};
@@ -80,9 +97,35 @@ int write_aovs(rt_scene_t scene, Camera camera, int width, int height, const std
             return 1;
         }
     }
-    rt_free(b.depth);
-    rt_free(b.normal);
-    rt_free(b.albedo);
+    return 0;
+}
+
+// "dir/x.png" -> "dir/x.denoised.png" (a name without an extension gets the suffix appended)
+std::string denoised_path(const std::string &out)
+{
+    const size_t slash = out.find_last_of('/');
+    const size_t dot = out.find_last_of('.');
+    const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash + 1);
+    return (has_ext ? out.substr(0, dot) : out) + ".denoised.png";
+}
+
+// --denoise: rt_denoise -> rt_tonemap_rgb -> PNG with save_render's vertical flip (rt/save_render.cuh:55)
+int write_denoised(G_Buffer g_buffer, const RtAovBuffers &b, int width, int height, const std::string &path)
+{
+    const size_t n = (size_t)width * height;
+    float *rgb = nullptr;
+    uint8_t *rgba = nullptr;
+    if (rt_device_alloc((void **)&rgb, n * 12) != RT_OK || rt_device_alloc((void **)&rgba, n * 4) != RT_OK)
+        return fail("denoise buffers");
+    if (rt_denoise(g_buffer, &b, width, height, rgb, nullptr) != RT_OK) return fail("denoise");
+    if (rt_tonemap_rgb(rgb, rgba, width, height, nullptr) != RT_OK) return fail("tonemap_rgb");
+    std::vector<uint8_t> img(n * 4), flipped(n * 4);
+    if (rt_download(img.data(), rgba, n * 4) != RT_OK) return fail("denoised download");
+    rt_free(rgb);
+    rt_free(rgba);
+    for (int y = 0; y < height; ++y)
+        memcpy(&flipped[(size_t)(height - y - 1) * width * 4], &img[(size_t)y * width * 4], (size_t)width * 4);
+    if (rt_write_png(path.c_str(), flipped.data(), width, height) != RT_OK) return fail("write denoised png");
     return 0;
 }
 
@@ -94,7 +137,7 @@ int main(int argc, char **argv)
     int width = 1920, height = 1080, spp = 5000, passes = 64, adaptive = 1, min_samples = 100, max_depth = 0;
     int device = 0, shard_id = 0, num_shards = 1, kernel = RT_KERNEL_WAVEFRONT;
     float tolerance = 0.05f;
-    bool quiet = false;
+    bool quiet = false, denoise = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&](void) -> const char * {
@@ -122,6 +165,7 @@ int main(int argc, char **argv)
         else if (a == "--checkpoint") checkpoint = next();
         else if (a == "--resume") resume = next();
         else if (a == "--aov") aov = next();
+        else if (a == "--denoise") denoise = true;
         else {
             usage();
             return 2;
@@ -155,7 +199,12 @@ int main(int argc, char **argv)
     rt_host_scene_destroy(host);
     const double setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
-    if (!aov.empty() && write_aovs(prepared, camera, width, height, aov) != 0) return 1;
+    RtAovBuffers aov_buffers = {nullptr, nullptr, nullptr, nullptr};
+    if (!aov.empty()) {
+        if (render_aovs(prepared, camera, width, height, &aov_buffers) != 0) return 1;
+        if (write_aovs(aov_buffers, width, height, aov) != 0) return 1;
+        if (!denoise) free_aovs(&aov_buffers);
+    }
 
     RtOptions opt;
     rt_default_options(&opt);
@@ -189,6 +238,13 @@ int main(int argc, char **argv)
     if (rt_save_render(g_buffer, width, height, out.c_str()) != RT_OK) return fail("save_render");
     printf("rendered %dx%d x %d spp in %.3f s (%.2f Msamples/s nominal; scene setup %.2f s) -> %s\n", width, height,
            spp, render_s, (double)width * height * spp / render_s / 1e6, setup_s, out.c_str());
+    if (denoise) {
+        if (!aov_buffers.depth && render_aovs(prepared, camera, width, height, &aov_buffers) != 0) return 1;
+        const std::string path = denoised_path(out);
+        if (write_denoised(g_buffer, aov_buffers, width, height, path) != 0) return 1;
+        if (!quiet) printf("denoised -> %s\n", path.c_str());
+        free_aovs(&aov_buffers);
+    }
 
     rt_scene_release(prepared);
     rt_destroy_scene(&scene);

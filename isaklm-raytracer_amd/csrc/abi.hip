@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "denoise_math.h"
 #include "host/rt_host.h"
 
 int rt_launch_path(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera &cam, int stack_depth,
@@ -38,6 +39,12 @@ int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width
                          hipStream_t stream);
 int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *rays, hipStream_t stream);
 void rt_query_shutdown();
+// denoise.hip
+int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const float *depth, const float *normal,
+                      const float *albedo, int width, int height, float *rgb_out, const RtDnParams &prm,
+                      hipStream_t stream);
+int rt_launch_tonemap_rgb(const float *rgb, RtUChar4 *out, int n, hipStream_t stream);
+void rt_denoise_shutdown();
 
 static thread_local std::string g_error;
 
@@ -222,6 +229,7 @@ void rt_shutdown(void)
     rt_wavefront_shutdown();
     rt_path_shutdown();
     rt_query_shutdown();
+    rt_denoise_shutdown();
     std::lock_guard<std::mutex> g(g_dev_mu);
     for (auto &kv : g_dev_stats) {
         if (hipSetDevice(kv.first) == hipSuccess) (void)hipFree(kv.second);
@@ -897,9 +905,10 @@ int rt_trace_rays(rt_scene_t scene, const float *rays, long long n, RtRayHit *hi
     return RT_OK;
 }
 
-static int frame_size_ok(const char *who, int width, int height)
+// (min_width 2: the camera's half width divides; the denoiser has no camera and takes a 1-pixel column)
+static int frame_size_ok(const char *who, int width, int height, int min_width = 2)
 {
-    if (width < 2 || height <= 0 || (long long)width * height > (1LL << 31) - 1) {
+    if (width < min_width || height <= 0 || (long long)width * height > (1LL << 31) - 1) {
         rt_set_error("%s: bad frame size %d x %d", who, width, height);
         return RT_E_INVALID;
     }
@@ -953,6 +962,55 @@ int rt_tonemap(G_Buffer g, uint8_t *rgba, int w, int h, void *stream)
     if (jr != RT_OK) return jr;
     if (rt_launch_tonemap(g.frame_buffer, g.sample_count, (RtUChar4 *)rgba, w * h, (hipStream_t)stream) != 0) {
         rt_set_error("rt_tonemap: launch failed");
+        return RT_E_HIP;
+    }
+    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
+}
+
+// ---------------- denoising (denoise.hip; rt_denoise_host and the default options: host/denoise_host.cpp) ----------------
+int rt_denoise(G_Buffer g, const RtAovBuffers *aov, int width, int height, float *rgb_out, const RtDenoiseOptions *opt)
+{
+    RtDnParams prm;
+    if (!rt_dn_resolve(opt, &prm)) {
+        rt_set_error("rt_denoise: option out of range (iterations 1..%d, normal_log2 1..%d, demodulate -1..1, "
+                     "sigmas finite and >= 0)", RT_DN_MAX_ITERATIONS, RT_DN_MAX_NORMAL_LOG2);
+        return RT_E_INVALID;
+    }
+    if (!g.frame_buffer || !g.squared_luminance || !g.sample_count || !rgb_out || !aov || !aov->depth ||
+        !aov->normal || (prm.demodulate && !aov->albedo)) {
+        rt_set_error("rt_denoise: null G_Buffer array, AOV buffer or output");
+        return RT_E_INVALID;
+    }
+    if (misaligned(rgb_out, 4) || misaligned(aov->depth, 4) || misaligned(aov->normal, 4) || misaligned(aov->albedo, 4)) {
+        rt_set_error("rt_denoise: misaligned buffer");
+        return RT_E_INVALID;
+    }
+    const int rc = frame_size_ok("rt_denoise", width, height, 1);
+    if (rc != RT_OK) return rc;
+    hipStream_t stream = (hipStream_t)(opt ? opt->stream : nullptr);
+    const int jr = join_status(stream, "rt_denoise"); // chained renders' deep-path tails first, as rt_tonemap
+    if (jr != RT_OK) return jr;
+    rt_register_shutdown();
+    if (rt_launch_denoise(g.frame_buffer, g.squared_luminance, g.sample_count, aov->depth, aov->normal, aov->albedo,
+                          width, height, rgb_out, prm, stream) != 0) {
+        rt_set_error("rt_denoise: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return RT_E_HIP;
+    }
+    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
+}
+
+int rt_tonemap_rgb(const float *rgb, uint8_t *rgba, int w, int h, void *stream)
+{
+    if (!rgb || !rgba || misaligned(rgb, 4) || misaligned(rgba, 4)) {
+        rt_set_error("rt_tonemap_rgb: null or misaligned buffer");
+        return RT_E_INVALID;
+    }
+    const int rc = frame_size_ok("rt_tonemap_rgb", w, h, 1);
+    if (rc != RT_OK) return rc;
+    if (rt_launch_tonemap_rgb(rgb, (RtUChar4 *)rgba, w * h, (hipStream_t)stream) != 0) {
+        rt_set_error("rt_tonemap_rgb: launch failed");
         return RT_E_HIP;
     }
     if (!stream) HIPCHK(hipStreamSynchronize(nullptr));

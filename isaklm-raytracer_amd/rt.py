@@ -76,6 +76,11 @@ class RtAovBuffers(ctypes.Structure):
                 ("triangle", ctypes.c_void_p)]
 
 
+class RtDenoiseOptions(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("sigma_lum", ctypes.c_float), ("sigma_depth", ctypes.c_float),
+                ("normal_log2", ctypes.c_int), ("demodulate", ctypes.c_int), ("stream", ctypes.c_void_p)]
+
+
 # RtRayHit (16 B) and RtRaySurface (80 B) as numpy record types
 RAY_HIT = np.dtype([("triangle", np.int32), ("bx", np.float32), ("by", np.float32), ("bz", np.float32)])
 RAY_SURFACE = np.dtype([("position", np.float32, 3), ("t", np.float32), ("normal", np.float32, 3),
@@ -144,7 +149,7 @@ def join(stream=None):
     check(lib().rt_join(stream))
 
 
-ABI_VERSION = 10  # RT_ABI_VERSION of include/isaklm_rt.h
+ABI_VERSION = 11  # RT_ABI_VERSION of include/isaklm_rt.h
 E_INCOMPLETE = -7  # RT_E_INCOMPLETE: a join found stranded pixels
 DEBUG_CALL_LOG, DEBUG_LONG_LOG, DEBUG_CHECK_FAULT, DEBUG_LONG_QUIT = 1, 2, 4, 8  # RtOptions.debug bits
 DEBUG_SERIAL_LONG_FIRST, DEBUG_SERIAL_FIN_FIRST = 16, 32  # (tests: serialised dispatch in either order)
@@ -221,6 +226,11 @@ def lib():
         L.rt_trace_rays.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, ctypes.POINTER(RtQueryOptions)]
         L.rt_camera_rays.argtypes = [Camera, i, i, vp, vp]
         L.rt_render_aov.argtypes = [vp, Camera, i, i, ctypes.POINTER(RtAovBuffers), ctypes.POINTER(RtQueryOptions)]
+        L.rt_default_denoise_options.argtypes = [ctypes.POINTER(RtDenoiseOptions)]
+        L.rt_default_denoise_options.restype = None
+        L.rt_denoise.argtypes = [G_Buffer, ctypes.POINTER(RtAovBuffers), i, i, vp, ctypes.POINTER(RtDenoiseOptions)]
+        L.rt_denoise_host.argtypes = [vp, vp, vp, vp, vp, vp, i, i, vp, ctypes.POINTER(RtDenoiseOptions)]
+        L.rt_tonemap_rgb.argtypes = [vp, vp, i, i, vp]
         L.rt_shutdown.restype = None
         L.rt_abi_version.restype = i
         if L.rt_abi_version() != ABI_VERSION:
@@ -561,6 +571,93 @@ def render_aov(dscene, camera, width, height, traversal=None):
         check(L.rt_render_aov(dscene.prepared, camera, width, height, ctypes.byref(b), ctypes.byref(o)))
         for name, d in (("depth", d_depth), ("normal", d_normal), ("albedo", d_albedo), ("triangle", d_tri)):
             check(L.rt_download(_ptr(out[name]), d, out[name].nbytes))
+    return out
+
+
+# ---------------------------------------------------------------- denoising
+def denoise_options(iterations=0, sigma_lum=0.0, sigma_depth=0.0, normal_log2=0, demodulate=True, stream=None):
+    """RtDenoiseOptions; 0 = the library default (5 levels, sigma_lum 4, sigma_depth 1, normal_log2 7);
+    demodulate False filters the colour itself (no albedo needed); stream: an integer hipStream_t."""
+    o = RtDenoiseOptions()
+    o.iterations, o.sigma_lum, o.sigma_depth, o.normal_log2 = iterations, sigma_lum, sigma_depth, normal_log2
+    o.demodulate = 1 if demodulate else -1
+    o.stream = stream
+    return o
+
+
+def denoise_device(g, aov_ptrs, width, height, out_ptr, **options):
+    """rt_denoise on device memory: g a G_Buffer struct, aov_ptrs (depth, normal, albedo) integer device
+    pointers (albedo may be None with demodulate=False), out_ptr width*height*3 floats."""
+    b = RtAovBuffers(_int_ptr(aov_ptrs[0]), _int_ptr(aov_ptrs[1]), _int_ptr(aov_ptrs[2]), None)
+    o = denoise_options(**options)
+    check(lib().rt_denoise(g, ctypes.byref(b), width, height, _int_ptr(out_ptr), ctypes.byref(o)))
+
+
+def denoise(gbuf, aov, **options):
+    """rt_denoise: the denoised mean radiance of `gbuf` as (H, W, 3) float32, row 0 = bottom.  aov: the dict
+    rt.render_aov returns (numpy arrays, uploaded here) or a dict of integer device pointers; keys depth,
+    normal and — unless demodulate=False — albedo.  Options: denoise_options."""
+    W, H = gbuf.width, gbuf.height
+    n = W * H
+    L = lib()
+    out = np.zeros((H, W, 3), np.float32)
+    names = ("depth", "normal", "albedo")
+    host = {k: np.ascontiguousarray(aov[k], dtype=np.float32) for k in names
+            if aov.get(k) is not None and isinstance(aov[k], np.ndarray)}
+    with _DeviceBytes(n * 4) as d_depth, _DeviceBytes(n * 12) as d_normal, _DeviceBytes(n * 12) as d_albedo, \
+            _DeviceBytes(n * 12) as d_out:
+        ptrs = []
+        for k, d in zip(names, (d_depth, d_normal, d_albedo)):
+            if k in host:
+                if host[k].size != n * (1 if k == "depth" else 3):
+                    raise ValueError(f"aov[{k!r}] does not match the {W} x {H} frame")
+                check(L.rt_upload(d, _ptr(host[k]), host[k].nbytes))
+                ptrs.append(d)
+            else:
+                ptrs.append(aov.get(k))
+        denoise_device(gbuf.g, ptrs, W, H, d_out, **options)
+        _synchronize_stream(options.get("stream"))
+        check(L.rt_download(_ptr(out), d_out, out.nbytes))
+    return out
+
+
+def denoise_host(fb, sq, count, depth, normal, albedo, **options):
+    """rt_denoise_host: rt_denoise's arithmetic on the CPU, bit-identical to the GPU.  fb (H, W, 3), sq and
+    count (H, W), depth (H, W), normal and albedo (H, W, 3) (albedo may be None with demodulate=False); the
+    frame size is taken from depth's shape.  Returns (H, W, 3) float32."""
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if depth.ndim != 2:
+        raise ValueError("depth must have shape (H, W)")
+    H, W = depth.shape
+    n = W * H
+
+    def arr(a, dtype, per):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.size != n * per:
+            raise ValueError("buffer does not match the frame size")
+        return a
+    fb, sq, count = arr(fb, np.float32, 3), arr(sq, np.float32, 1), arr(count, np.int32, 1)
+    normal = arr(normal, np.float32, 3)
+    albedo = None if albedo is None else arr(albedo, np.float32, 3)
+    out = np.zeros((H, W, 3), np.float32)
+    o = denoise_options(**options)
+    check(lib().rt_denoise_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(depth), _ptr(normal),
+                                None if albedo is None else _ptr(albedo), W, H, _ptr(out), ctypes.byref(o)))
+    return out
+
+
+def tonemap_rgb(rgb):
+    """rt_tonemap_rgb: rt_tonemap's colour math on an (H, W, 3) float32 mean-radiance image (e.g. denoise's
+    result) -> (H*W, 4) uint8, row 0 = bottom."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    H, W = rgb.shape[0], rgb.shape[1]
+    n = W * H
+    out = np.zeros((n, 4), dtype=np.uint8)
+    L = lib()
+    with _DeviceBytes(rgb.nbytes) as d_rgb, _DeviceBytes(n * 4) as d_out:
+        check(L.rt_upload(d_rgb, _ptr(rgb), rgb.nbytes))
+        check(L.rt_tonemap_rgb(d_rgb, d_out, W, H, None))
+        check(L.rt_download(_ptr(out), d_out, out.nbytes))
     return out
 
 
