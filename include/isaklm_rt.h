@@ -64,11 +64,12 @@ extern "C" {
  * rt_camera_rays, rt_render_aov, RtRayHit, RtRaySurface, RtQueryOptions,
  * RtAovBuffers): an addition only; 11 = the denoiser (rt_denoise,
  * rt_denoise_host, rt_default_denoise_options, RtDenoiseOptions) and
- * rt_tonemap_rgb: additions only.
+ * rt_tonemap_rgb: additions only; 12 = the occlusion query (rt_occluded):
+ * an addition only.
  * An integrator checks
  * rt_abi_version() == RT_ABI_VERSION at start-up: a binary built against an
  * older header would otherwise link (C linkage) and mis-pass arguments. */
-#define RT_ABI_VERSION 11
+#define RT_ABI_VERSION 12
 
 /* CUDA uchar4, used for texels (rt/scene.cuh:18) */
 typedef struct RtUChar4 { uint8_t x, y, z, w; } RtUChar4;
@@ -672,6 +673,32 @@ typedef struct RtAovBuffers { float *depth; float *normal; float *albedo; int32_
  * rays. */
 int rt_render_aov(rt_scene_t scene, Camera camera, int width, int height, const RtAovBuffers *buffers,
                   const RtQueryOptions *opt);
+
+/* ---------------- occlusion queries (ABI 12) ----------------
+ * "Is anything in the way?" — shadow rays, point-to-point visibility, ambient occlusion, line of sight.
+ * occluded_device[i] = 1 if the reference's trace_ray (rt/trace_ray.cuh:244-318) on ray i returns a hit
+ * whose ray parameter s -- the *t of the winning intersect_triangle (rt/trace_ray.cuh:90-97), the value
+ * trace_leaf_node's smallest_t ends on -- satisfies s < tmax_device[i] (a float32 compare); else 0.
+ * tmax_device NULL = +inf for every ray (the result is then rt_trace_rays' hit flag).
+ *
+ * So for every ray and every tmax the answer is (rt_trace_rays hits) && (s < tmax), bit for bit, in either
+ * traversal mode — the reference's first-leaf rule and its s >= 1e-5 rule included: a ray with
+ * !(tmax > 1e-5f) (NaN, zero, negative, -inf, 1e-5f itself) is never occluded and is not traced, and no
+ * self-intersection offset is needed beyond the reference's own 1e-5.
+ *
+ * rays_device: rt_trace_rays' layout and rules (n x 6 floats, 8-B aligned, used as given, never
+ * normalised, any floats).  tmax_device: n floats, 4-B aligned, in units of the ray parameter: a distance
+ * when the direction has unit length.  Prefer normalised directions with tmax = |q - p| for a segment
+ * p -> q: d = q - p with tmax = 1 is answered too, but such a direction usually lies outside the bounded
+ * traversal's domain (0.5 <= max|d_i| <= 2) and takes the plain KD traversal.  occluded_device: n bytes at
+ * any alignment; no byte outside [0, n) is written.
+ *
+ * n == 0: RT_OK without a launch; a null scene, rays or output, a misaligned rays or tmax pointer, n < 0,
+ * n > 2^31 - 1: RT_E_INVALID before any GPU call.  opt NULL = the defaults; traversal and stream as for
+ * rt_trace_rays; stats_device adds [0] rays, [1] occluded rays, [2] rays that ran the plain KD traversal
+ * (a ray rejected by the tmax rule counts in [0] only).  Ordering: as the other query calls (above). */
+int rt_occluded(rt_scene_t scene, const float *rays_device, const float *tmax_device, long long n,
+                uint8_t *occluded_device, const RtQueryOptions *opt);
 
 /* draw_frame's colour math (rt/render.cuh:37-59): correct_color(fb/count) ->
  * RGBA8 into a device buffer of width*height*4 bytes, row 0 = bottom. */

@@ -38,6 +38,8 @@ int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width
                          float *normal, float *albedo, int *triangle, int traversal, unsigned long long *stats,
                          hipStream_t stream);
 int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *rays, hipStream_t stream);
+int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tmax, long long n, uint8_t *occluded,
+                       int traversal, unsigned long long *stats, hipStream_t stream);
 void rt_query_shutdown();
 // denoise.hip
 int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const float *depth, const float *normal,
@@ -899,6 +901,29 @@ int rt_trace_rays(rt_scene_t scene, const float *rays, long long n, RtRayHit *hi
     hipStream_t stream = (hipStream_t)o.stream;
     if (rt_launch_trace_rays(scene->dev, rays, n, hits, surface, o.traversal, o.stats_device, stream) != 0) {
         rt_set_error("rt_trace_rays: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return RT_E_HIP;
+    }
+    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
+}
+
+int rt_occluded(rt_scene_t scene, const float *rays, const float *tmax, long long n, uint8_t *occluded,
+                const RtQueryOptions *opt)
+{
+    RtQueryOptions o;
+    if (!rays || !occluded) { rt_set_error("rt_occluded: null rays or output"); return RT_E_INVALID; }
+    if (n < 0 || n > (1LL << 31) - 1) { rt_set_error("rt_occluded: n = %lld out of [0, 2^31 - 1]", n); return RT_E_INVALID; }
+    if (misaligned(rays, 8) || misaligned(tmax, 4)) {
+        rt_set_error("rt_occluded: misaligned pointer (rays 8 B, tmax 4 B)");
+        return RT_E_INVALID;
+    }
+    const int rc = query_options("rt_occluded", scene, opt, &o);
+    if (rc != RT_OK) return rc;
+    if (n == 0) return RT_OK;
+    rt_register_shutdown();
+    hipStream_t stream = (hipStream_t)o.stream;
+    if (rt_launch_occluded(scene->dev, rays, tmax, n, occluded, o.traversal, o.stats_device, stream) != 0) {
+        rt_set_error("rt_occluded: launch failed: %s", hipGetErrorString(hipGetLastError()));
         return RT_E_HIP;
     }
     if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));

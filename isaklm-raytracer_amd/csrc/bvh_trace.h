@@ -470,4 +470,136 @@ __device__ __forceinline__ bool trace_bvh_park(const RtDevScene &sc, const Vec3D
     return true;
 }
 
+// ---- the occlusion query (rt_occluded, query.hip) ----
+// kd_bounded restated so that it yields the winning ray parameter instead of
+// the barycentrics: hs = the *t of the winning intersect_triangle
+// (rt/trace_ray.cuh:90-97), the value trace_leaf_node's smallest_t ends on
+// (`st` in the T* leaf, `smallest` after leaf_scan).  The descent, the T*
+// leaf and the leaf scan are kd_bounded's, statement for statement; with
+// s_min = -inf and tstar = -1 it is the plain traversal, trace().  A function
+// of its own: the render kernels' kd_bounded stays as it is.
+template <typename STACK>
+__device__ __forceinline__ int kd_bounded_s(const RtDevScene &sc, const Vec3D o, const Vec3D d, float entry,
+                                            const float root_exit, const float s_min, const int tstar, float &hs,
+                                            STACK &stk, Cnt &c)
+{
+    float exit_ = root_exit;
+    const float yx = rt_recip_guard(d.x), yy = rt_recip_guard(d.y), yz = rt_recip_guard(d.z);
+    int sp = 0;
+    uint32_t node = 0;
+    while (true) {
+        uint2 nd = ldc_u2(sc.nodes + 2 * (size_t)node);
+        while ((nd.y & 3u) != RT_LEAF_TAG) {
+            const uint32_t axis = nd.y & 3u;
+            const float split = as_float(nd.x);
+            const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
+            const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
+            const float yax = axis == 0 ? yx : (axis == 1 ? yy : yz);
+            uint32_t near_c = node + 1, far_c = nd.y >> 2;
+            if (oax >= split) { // ray_behind_plane (:174-188)
+                near_c = nd.y >> 2;
+                far_c = node + 1;
+            }
+            const float t = rt_div_by(split - oax, dax, yax); // intersect_plane (:190-210)
+            if (t >= exit_ || t < 0) {
+                node = near_c;
+            } else if (t <= entry) {
+                node = far_c;
+            } else if (t <= s_min) { // the near side holds no hit: its leaves' exits are <= t
+                node = far_c;
+                entry = t;
+            } else {
+                stk.put(sp, far_c, t);
+                ++sp;
+                node = near_c;
+                exit_ = t;
+            }
+            nd = ldc_u2(sc.nodes + 2 * (size_t)node);
+        }
+        const uint32_t count = nd.y >> 2;
+        if (count > 0 && exit_ > s_min) {
+            // trace_leaf_node (:115-172): closest starts at the leaf's exit
+            float smallest = exit_;
+            float bx = 0.0f, by = 0.0f, bz = 0.0f;
+            int be = -1;
+            const uint32_t e0 = nd.x, e1 = nd.x + count;
+            if (tstar >= 0) { // the T* leaf (kd_bounded)
+                uint32_t at = e1;
+                for (uint32_t e = e0; e < e1 && at == e1; e += 4) {
+                    uint32_t id[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) id[k] = *(const RT_CONST uint32_t *)(sc.isect_tri + (e + k < e1 ? e + k : e));
+#pragma unroll
+                    for (int k = 3; k >= 0; --k)
+                        if (e + k < e1 && id[k] == (uint32_t)tstar) at = e + k;
+                }
+                if (at != e1) {
+                    float st;
+                    if (rt_tri_plane(ldc4(sc.isect_a + at), o, d, smallest, st) &&
+                        rt_tri_bary(ldc4(&sc.isect_bary[at].b), ldc4(&sc.isect_bary[at].c), ldc4(&sc.isect_bary[at].d),
+                                    ldc_f(&sc.isect_bary[at].rd), o, d, st, bx, by, bz)) {
+                        smallest = st;
+                        be = (int)at;
+                    }
+                }
+            }
+            if (be < 0) be = leaf_scan<false>(sc.isect_a, sc.isect_bary, e0, e1, o, d, smallest, bx, by, bz, c);
+            if (be >= 0) { // (the triangle index of a listed entry is >= 0)
+                hs = smallest;
+                return (int)ldc_u2(&sc.isect_bary[be].rd).y;
+            }
+        }
+        if (sp == 0) return -1;
+        --sp;
+        node = stk.node_at(sp);
+        entry = stk.entry_at(sp);
+        exit_ = sp > 0 ? stk.entry_at(sp - 1) : root_exit;
+    }
+}
+
+// trace_ray's hit and its ray parameter by the plain KD traversal (the rays
+// outside the bound's domain, RT_TRAVERSAL_KD): -1 = miss
+template <typename STACK>
+__device__ __forceinline__ int trace_s(const RtDevScene &sc, const Vec3D o, const Vec3D d, float &hs, STACK &stk,
+                                       Cnt &c)
+{
+    float entry, exit_;
+    if (!bbox_hit(sc, o, d, entry, exit_)) return -1;
+    return kd_bounded_s(sc, o, d, entry, exit_, -INFINITY, -1, hs, stk, c);
+}
+
+// Whether trace_ray hits with a ray parameter s < tmax (tmax > 1e-5: the
+// caller's rule), for a ray inside the bound's domain (rt_bounded_ray and
+// query.hip's gate).  The s_min query is capped at best0 = min(root exit,
+// tmax): when nothing passes below best0 the answer is "no" without any KD
+// descent — a reference hit needs s < its leaf's exit <= the root's exit, so
+// any hit has s >= tmax — and every BVH box entered beyond tmax is culled.
+// When something does, the capped query returns the uncapped one's s_min, T*
+// and tie mark (a box it culls is entered above best0 > s_min and holds
+// neither the minimum nor a tie of it; a test at s == best0 before any pass is
+// no pass, as at the root's exit), and the KD phase is trace_bvh's.
+// (No KD leaf is pruned by entry >= tmax: the reference's leaf test accepts s
+// below the leaf's entry.)
+// (early: whether the capped query alone answered — a counting build's figure, tools/occlusion_bench.py)
+template <typename STACK>
+__device__ __forceinline__ bool occluded_bvh(const RtDevScene &sc, const Vec3D o, const Vec3D d, const float tmax,
+                                             STACK &stk, Cnt &c, bool &early)
+{
+    early = false;
+    float entry, exit_;
+    if (!bbox_hit(sc, o, d, entry, exit_)) return false;
+    const float root_exit = exit_;
+    const float best0 = fminf(root_exit, tmax);
+    int tstar = -1;
+    const float s_min =
+        RT_BVH4 ? bvh4_bound<false>(sc, o, d, best0, stk, c, tstar) : bvh_bound<false>(sc, o, d, best0, stk, c);
+    if (!(s_min < best0)) {
+        early = true;
+        return false;
+    }
+    float s = INFINITY;
+    const int tri = kd_bounded_s(sc, o, d, entry, root_exit, s_min, tstar, s, stk, c);
+    return tri >= 0 && s < tmax;
+}
+
 } // namespace rtk

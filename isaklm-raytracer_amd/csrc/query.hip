@@ -1,5 +1,6 @@
-// query.hip — the batched ray query (rt_trace_rays), the camera-ray generator
-// (rt_camera_rays) and the first-hit AOV pass (rt_render_aov).
+// query.hip — the batched ray query (rt_trace_rays), the occlusion query
+// (rt_occluded), the camera-ray generator (rt_camera_rays) and the first-hit
+// AOV pass (rt_render_aov).
 //
 // The closest-hit query is the renderer's own: trace_ray (rt/trace_ray.cuh:
 // 244-318) as rt_kernels.h trace() restates it, sped up by the conservative
@@ -9,6 +10,8 @@
 //
 //   rt_trace_rays   rays from a buffer      -> hit (+ surface) records
 //   rt_render_aov   rays from the camera    -> planar AOV buffers
+// and a second kernel of the same shape for the any-hit question:
+//   rt_occluded     rays + tmax from buffers -> one byte per ray
 //
 // One ray per lane; the lanes of a wave take their next rays together from a
 // global counter (one wave-aggregated atomic per round).  The traversal stack
@@ -38,6 +41,9 @@
 #endif
 #ifndef RQ_WAVES
 #define RQ_WAVES 4 // waves per SIMD = resident blocks per CU
+#endif
+#ifndef RQ_COUNT_EARLY
+#define RQ_COUNT_EARLY 0 // 1: rt_occluded's stats get a fourth word (a counting build, never the shipped one)
 #endif
 
 using namespace rtk;
@@ -218,6 +224,85 @@ __global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
     }
 }
 
+// ---- the occlusion query (rt_occluded) ----
+struct BufferRaysTmax { // BufferRays and the ray's tmax (NULL: +inf for every ray)
+    BufferRays rays;
+    const float *tmax;
+    __device__ __forceinline__ void load(uint32_t e, Vec3D &o, Vec3D &d, float &t) const
+    {
+        rays.load(e, o, d);
+        t = tmax ? tmax[e] : INFINITY;
+    }
+};
+struct ByteSink { // one byte per ray, any alignment
+    uint8_t *out;
+    __device__ __forceinline__ void store(uint32_t e, bool occluded) const { out[e] = occluded ? 1 : 0; }
+};
+
+// rt_query_kernel's shape for the any-hit question: occluded[e] = trace_ray
+// hits ray e with a ray parameter s < tmax[e].  A ray with !(tmax > 1e-5) is
+// not traced (no test passes below 1e-5).  Inside the domain gate the capped
+// s_min query answers most unoccluded rays alone (bvh_trace.h occluded_bvh);
+// outside it the plain KD traversal gives the hit's s.  stats (optional) adds
+// [0] rays, [1] occluded rays, [2] rays that ran the plain KD traversal.
+// (RQ_COUNT_EARLY: a counting build for tools/occlusion_bench.py — stats then
+// has a fourth word, the rays the capped query answered alone.)
+template <typename SRC, typename SINK>
+__global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
+    rt_occluded_kernel(RtDevScene sc, SRC src, SINK sink, uint32_t n, int kd_only, uint32_t *fetch,
+                       unsigned long long *stats, uint2 *spill, int spill_threads)
+{
+    __shared__ uint32_t s_node[RQ_LDS * RQ_BLOCK];
+    __shared__ float s_entry[RQ_LDS * RQ_BLOCK];
+    const int tid = threadIdx.x;
+    const int gtid = blockIdx.x * RQ_BLOCK + tid;
+    Stack<RQ_LDS> stk{s_node + tid, s_entry + tid, RQ_BLOCK, spill + gtid, spill_threads};
+    Cnt c; // (never counted)
+    const int lane = __lane_id();
+    uint32_t n_rays = 0, n_occ = 0, n_kd = 0, n_early = 0;
+    while (true) {
+        const unsigned long long m = __ballot(true);
+        const int leader = __ffsll((long long)m) - 1;
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
+        base = __shfl(base, leader);
+        const uint32_t e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (e >= n) break; // (no wrap: as rt_query_kernel)
+        Vec3D o, d;
+        float tmax;
+        src.load(e, o, d, tmax);
+        bool occ = false;
+        if (tmax > 0.00001f) { // (false for a NaN)
+            if (!kd_only && direction_in_domain(d) && rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
+                bool early;
+                occ = occluded_bvh(sc, o, d, tmax, stk, c, early);
+                if (RQ_COUNT_EARLY && early) ++n_early;
+            } else {
+                float s = INFINITY;
+                occ = trace_s(sc, o, d, s, stk, c) >= 0 && s < tmax;
+                ++n_kd;
+            }
+        }
+        ++n_rays;
+        if (occ) ++n_occ;
+        sink.store(e, occ);
+    }
+    if (stats) { // (every lane of the wave is here: the loop's exits reconverge)
+        n_rays = wave_sum(n_rays);
+        n_occ = wave_sum(n_occ);
+        n_kd = wave_sum(n_kd);
+        if (lane == 0) {
+            if (n_rays) atomicAdd(stats + 0, (unsigned long long)n_rays);
+            if (n_occ) atomicAdd(stats + 1, (unsigned long long)n_occ);
+            if (n_kd) atomicAdd(stats + 2, (unsigned long long)n_kd);
+        }
+        if (RQ_COUNT_EARLY) {
+            n_early = wave_sum(n_early);
+            if (lane == 0 && n_early) atomicAdd(stats + 3, (unsigned long long)n_early);
+        }
+    }
+}
+
 // rt_camera_rays: ray y*W + x = the centre of pixel (x, y), three 8-B stores per lane
 __global__ void __launch_bounds__(RQ_BLOCK) rt_camera_rays_kernel(CameraRays src, float2 *rays, uint32_t n)
 {
@@ -252,8 +337,12 @@ std::map<int, QueryWorkspace> g_query;
 // max(RT_STACK_DEPTH, RT_BVH_STACK) entries in all: the KD part needs <= RT_STACK_DEPTH, the BVH part <= RT_BVH_STACK
 constexpr int kSpillDepth = (RT_BVH_STACK > RT_STACK_DEPTH ? RT_BVH_STACK : RT_STACK_DEPTH) - RQ_LDS;
 
+// (kernel: rt_query_kernel or rt_occluded_kernel — one signature, one workspace)
 template <typename SRC, typename SINK>
-int launch_query(const RtDevScene &sc, const SRC &src, const SINK &sink, long long n, int traversal,
+using QueryKernel = void (*)(RtDevScene, SRC, SINK, uint32_t, int, uint32_t *, unsigned long long *, uint2 *, int);
+
+template <typename SRC, typename SINK>
+int launch_query(QueryKernel<SRC, SINK> kernel, const RtDevScene &sc, const SRC &src, const SINK &sink, long long n, int traversal,
                  unsigned long long *stats, hipStream_t stream)
 {
     int dev = 0;
@@ -285,8 +374,8 @@ int launch_query(const RtDevScene &sc, const SRC &src, const SINK &sink, long lo
     const long long need = (n + RQ_BLOCK - 1) / RQ_BLOCK;
     const int grid = (int)(need < (long long)w.blocks ? need : (long long)w.blocks);
     const int kd_only = traversal == RT_TRAVERSAL_KD || sc.bvh_nodes == nullptr || sc.bvh4 == nullptr;
-    hipLaunchKernelGGL((rt_query_kernel<SRC, SINK>), dim3(grid), dim3(RQ_BLOCK), 0, stream, sc, src, sink, (uint32_t)n,
-                       kd_only, w.fetch, stats, w.spill, (int)w.spill_threads);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(RQ_BLOCK), 0, stream, sc, src, sink, (uint32_t)n, kd_only, w.fetch, stats,
+                       w.spill, (int)w.spill_threads);
     if (hipGetLastError() != hipSuccess || hipEventRecord(w.last, stream) != hipSuccess) return -1;
     w.recorded = true;
     return 0;
@@ -310,7 +399,15 @@ int rt_launch_trace_rays(const RtDevScene &sc, const float *rays, long long n, v
 {
     const BufferRays src{reinterpret_cast<const float2 *>(rays)};
     const RecordSink sink{reinterpret_cast<float4 *>(hits), reinterpret_cast<float4 *>(surface)};
-    return launch_query(sc, src, sink, n, traversal, stats, stream);
+    return launch_query(rt_query_kernel<BufferRays, RecordSink>, sc, src, sink, n, traversal, stats, stream);
+}
+
+int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tmax, long long n, uint8_t *occluded,
+                       int traversal, unsigned long long *stats, hipStream_t stream)
+{
+    const BufferRaysTmax src{BufferRays{reinterpret_cast<const float2 *>(rays)}, tmax};
+    const ByteSink sink{occluded};
+    return launch_query(rt_occluded_kernel<BufferRaysTmax, ByteSink>, sc, src, sink, n, traversal, stats, stream);
 }
 
 int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width, int height, float *depth,
@@ -318,8 +415,8 @@ int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width
                          hipStream_t stream)
 {
     const AovSink sink{depth, normal, albedo, triangle};
-    return launch_query(sc, camera_source(cam, width, height), sink, (long long)width * height, traversal, stats,
-                        stream);
+    return launch_query(rt_query_kernel<CameraRays, AovSink>, sc, camera_source(cam, width, height), sink,
+                        (long long)width * height, traversal, stats, stream);
 }
 
 int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *rays, hipStream_t stream)

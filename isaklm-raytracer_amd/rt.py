@@ -149,7 +149,7 @@ def join(stream=None):
     check(lib().rt_join(stream))
 
 
-ABI_VERSION = 11  # RT_ABI_VERSION of include/isaklm_rt.h
+ABI_VERSION = 12  # RT_ABI_VERSION of include/isaklm_rt.h
 E_INCOMPLETE = -7  # RT_E_INCOMPLETE: a join found stranded pixels
 DEBUG_CALL_LOG, DEBUG_LONG_LOG, DEBUG_CHECK_FAULT, DEBUG_LONG_QUIT = 1, 2, 4, 8  # RtOptions.debug bits
 DEBUG_SERIAL_LONG_FIRST, DEBUG_SERIAL_FIN_FIRST = 16, 32  # (tests: serialised dispatch in either order)
@@ -224,6 +224,7 @@ def lib():
         L.rt_default_query_options.argtypes = [ctypes.POINTER(RtQueryOptions)]
         L.rt_default_query_options.restype = None
         L.rt_trace_rays.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, ctypes.POINTER(RtQueryOptions)]
+        L.rt_occluded.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, ctypes.POINTER(RtQueryOptions)]
         L.rt_camera_rays.argtypes = [Camera, i, i, vp, vp]
         L.rt_render_aov.argtypes = [vp, Camera, i, i, ctypes.POINTER(RtAovBuffers), ctypes.POINTER(RtQueryOptions)]
         L.rt_default_denoise_options.argtypes = [ctypes.POINTER(RtDenoiseOptions)]
@@ -544,6 +545,53 @@ def trace_rays(dscene, rays, surface=False, traversal=None, stream=None, stats=F
             check(L.rt_download(_ptr(st), d_st, st.nbytes))
     out = (hits,) + ((surf,) if surface else ()) + ((dict(zip(QUERY_STATS, (int(v) for v in st))),) if stats else ())
     return out[0] if len(out) == 1 else out
+
+
+OCCLUSION_STATS = ("rays", "occluded", "kd_rays")  # rt_occluded's stats_device [0..2]
+
+
+def occluded_device(dscene, rays_ptr, tmax_ptr, n, out_ptr, traversal=None, stream=None, stats_ptr=None):
+    """rt_occluded on device memory: integer device pointers (a torch tensor's data_ptr()) to n x 6 float32
+    rays, n float32 tmax (None: +inf for every ray) and n output bytes (any alignment); stream: an integer
+    hipStream_t (torch.cuda.current_stream().cuda_stream) — the call is then only enqueued."""
+    o = query_options(traversal, stream, _int_ptr(stats_ptr))
+    check(lib().rt_occluded(dscene.prepared, _int_ptr(rays_ptr), _int_ptr(tmax_ptr), int(n), _int_ptr(out_ptr),
+                            ctypes.byref(o)))
+
+
+def occluded(dscene, rays, tmax=None, traversal=None, stream=None, stats=False):
+    """Whether anything lies on `rays` — a numpy (n, 6) float32 array as for trace_rays — before `tmax` (a
+    scalar or an (n,) array in units of the ray parameter; None: +inf): a uint8 array, 1 where the
+    reference's trace_ray hits with a ray parameter s < tmax.  With stats=True also a dict of the call's
+    counts (OCCLUSION_STATS)."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must have shape (n, 6)")
+    n = len(rays)
+    if tmax is not None:
+        tmax = np.asarray(tmax, dtype=np.float32)
+        if tmax.ndim not in (0, 1) or (tmax.ndim == 1 and len(tmax) != n):
+            raise ValueError("tmax must be a scalar or have shape (n,)")
+        tmax = np.ascontiguousarray(np.broadcast_to(tmax, (n,)))
+    L = lib()
+    out = np.zeros(n, dtype=np.uint8)
+    st = np.zeros(3, dtype=np.uint64)
+    with _DeviceBytes(rays.nbytes) as d_rays, _DeviceBytes(4 * n) as d_tmax, _DeviceBytes(n) as d_out, \
+            _DeviceBytes(st.nbytes) as d_st:
+        if n:
+            check(L.rt_upload(d_rays, _ptr(rays), rays.nbytes))
+            if tmax is not None:
+                check(L.rt_upload(d_tmax, _ptr(tmax), tmax.nbytes))
+        if stats:
+            check(L.rt_memset(d_st, 0, st.nbytes))
+        occluded_device(dscene, d_rays, d_tmax if tmax is not None else None, n, d_out, traversal, stream,
+                        d_st if stats else None)
+        _synchronize_stream(stream)
+        if n:
+            check(L.rt_download(_ptr(out), d_out, out.nbytes))
+        if stats:
+            check(L.rt_download(_ptr(st), d_st, st.nbytes))
+    return (out, dict(zip(OCCLUSION_STATS, (int(v) for v in st)))) if stats else out
 
 
 def camera_rays(camera, width, height):
