@@ -65,7 +65,10 @@ extern "C" {
  * RtAovBuffers): an addition only; 11 = the denoiser (rt_denoise,
  * rt_denoise_host, rt_default_denoise_options, RtDenoiseOptions) and
  * rt_tonemap_rgb: additions only; 12 = the occlusion query (rt_occluded):
- * an addition only.
+ * an addition only.  The radiance query (rt_trace_paths, RtPathOptions,
+ * rt_default_path_options) was added within version 12 — new symbols and a
+ * new struct, nothing existing moved; RT_HAS_TRACE_PATHS is its compile-time
+ * feature test.
  * An integrator checks
  * rt_abi_version() == RT_ABI_VERSION at start-up: a binary built against an
  * older header would otherwise link (C linkage) and mis-pass arguments. */
@@ -699,6 +702,55 @@ int rt_render_aov(rt_scene_t scene, Camera camera, int width, int height, const 
  * (a ray rejected by the tmax rule counts in [0] only).  Ordering: as the other query calls (above). */
 int rt_occluded(rt_scene_t scene, const float *rays_device, const float *tmax_device, long long n,
                 uint8_t *occluded_device, const RtQueryOptions *opt);
+
+/* ---------------- radiance queries (ABI 12, an addition) ----------------
+ * "What light arrives along this ray?" — light and irradiance probes, lightmap and vertex baking, panoramic,
+ * fisheye, orthographic or stereo cameras, radiance caches, re-rendering chosen pixels: the renderer's
+ * trace_path (rt/path_tracing.cuh:268-325) for the caller's own rays.
+ *
+ * For ray i (o, d = its 6 floats, used as given, never normalised) with st = rng_device[i], `samples` times:
+ *     (L, st) = trace_path(o, d, st)      started as the renderer starts a camera ray: ray type PRIMARY,
+ *                                         inside_medium false, throughput 1 — so the first hit's emission
+ *                                         counts, NEE follows diffuse events, the roulette is the reference's,
+ *                                         and a miss ends the path without a roulette draw (a ray whose first
+ *                                         trace_ray misses gives L = 0 and leaves st as it was);
+ *     radiance[i] = radiance[i] + L       component-wise float adds, in sample order;
+ *     sq[i] = sq[i] + luminance(L)^2      with the operations of rt/path_tracing.cuh:322-324;
+ * then rng_device[i] = st.  With accumulate = 0 the sums start at +0.0f, with accumulate = 1 at the buffers'
+ * contents (rt_render's frame_buffer / squared_luminance rule): k calls of 1 sample with accumulate = 1 after a
+ * first call with 0 equal one call of k samples bit for bit, and for a ray list that is a frame's camera
+ * samples the outputs are rt_render's frame_buffer, squared_luminance and random_numbers.  radiance is a SUM:
+ * divide by the number of samples taken.  Every value is the reference's bit for bit, in either traversal
+ * mode: for every ray whose direction has a magnitude within [2^-20, 2^20] (unnormalised, axis-parallel
+ * directions and origins outside the scene included), and for every ray whose first trace_ray hits nothing —
+ * among them every ray with a NaN or Inf component and every zero direction, which no intersect_triangle
+ * test passes: L = 0, the RNG state untouched.  (A finite direction far outside that range that hits
+ * something overflows in the reference's scatter arithmetic; its records then hold whatever that gives.)
+ *
+ * rays_device: n x 6 floats, 8-B aligned (rt_trace_rays' layout); rng_device: n uint32, read and written;
+ * radiance_device: n x 3 floats; sq_luminance_device: n floats or NULL; all 4-B aligned.  Nothing at index n
+ * or beyond is read or written.  n == 0: RT_OK without a launch; a null scene, rays, rng or radiance pointer, a
+ * misaligned pointer, n < 0, n > 2^31 - 1, samples, max_depth or accumulate out of range: RT_E_INVALID before
+ * any GPU call.  opt NULL = the defaults.
+ *
+ * Like the other queries it reads the prepared scene only — no G_Buffer, render workspace or chain, nothing
+ * added to rt_deviation_stats (cuts and the longest path go to stats_device) — and shares their per-device
+ * workspace and event ordering (released by rt_shutdown). */
+#define RT_HAS_TRACE_PATHS 1
+typedef struct RtPathOptions {
+    int samples;      /* paths per ray; 0 = default 1; 1 .. 1<<20 */
+    int max_depth;    /* as RtOptions.max_depth: 0 = unbounded (the 2^24-1 watchdog), else max extension rays */
+    int accumulate;   /* 0: outputs are written as (+0 + the samples); 1: the samples are added to what the
+                         output buffers hold (rt_render's fb/sq rule) */
+    int traversal;    /* RT_TRAVERSAL_BOUNDED (default) / RT_TRAVERSAL_KD; _BOUNDED_COUNTED is taken as BOUNDED */
+    void *stream;     /* hipStream_t; NULL = synchronous on the null stream */
+    unsigned long long *stats_device; /* optional, 5 u64: adds [0] rays, [1] paths, [2] trace_ray calls
+                         (extension + shadow rays, the oracle's RT_CNT_RAY meaning), [3] paths cut at the
+                         depth limit; [4] longest path in extension rays (atomic max, not a sum) */
+} RtPathOptions;
+void rt_default_path_options(RtPathOptions *opt);
+int rt_trace_paths(rt_scene_t scene, const float *rays_device, uint32_t *rng_device, long long n,
+                   float *radiance_device, float *sq_luminance_device, const RtPathOptions *opt);
 
 /* draw_frame's colour math (rt/render.cuh:37-59): correct_color(fb/count) ->
  * RGBA8 into a device buffer of width*height*4 bytes, row 0 = bottom. */

@@ -40,6 +40,9 @@ int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width
 int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *rays, hipStream_t stream);
 int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tmax, long long n, uint8_t *occluded,
                        int traversal, unsigned long long *stats, hipStream_t stream);
+int rt_launch_trace_paths(const RtDevScene &sc, const float *rays, uint32_t *rng, long long n, float *radiance, float *sq,
+                          int samples, int max_depth, int accumulate, int traversal, unsigned long long *stats,
+                          hipStream_t stream);
 void rt_query_shutdown();
 // denoise.hip
 int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const float *depth, const float *normal,
@@ -924,6 +927,54 @@ int rt_occluded(rt_scene_t scene, const float *rays, const float *tmax, long lon
     hipStream_t stream = (hipStream_t)o.stream;
     if (rt_launch_occluded(scene->dev, rays, tmax, n, occluded, o.traversal, o.stats_device, stream) != 0) {
         rt_set_error("rt_occluded: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return RT_E_HIP;
+    }
+    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
+}
+
+void rt_default_path_options(RtPathOptions *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->samples = 1;
+    o->traversal = RT_TRAVERSAL_BOUNDED;
+}
+
+int rt_trace_paths(rt_scene_t scene, const float *rays, uint32_t *rng, long long n, float *radiance, float *sq_luminance,
+                   const RtPathOptions *opt)
+{
+    RtPathOptions o;
+    if (opt) o = *opt; else rt_default_path_options(&o);
+    if (!scene) { rt_set_error("rt_trace_paths: null scene"); return RT_E_INVALID; }
+    if (!rays || !rng || !radiance) { rt_set_error("rt_trace_paths: null rays, rng or radiance"); return RT_E_INVALID; }
+    if (n < 0 || n > (1LL << 31) - 1) { rt_set_error("rt_trace_paths: n = %lld out of [0, 2^31 - 1]", n); return RT_E_INVALID; }
+    if (misaligned(rays, 8) || misaligned(rng, 4) || misaligned(radiance, 4) || misaligned(sq_luminance, 4) ||
+        misaligned(o.stats_device, 8)) {
+        rt_set_error("rt_trace_paths: misaligned pointer (rays and stats_device 8 B, rng, radiance and sq_luminance 4 B)");
+        return RT_E_INVALID;
+    }
+    if (o.samples < 0 || o.samples > (1 << 20) || o.max_depth < 0 || o.max_depth > RT_WATCHDOG_BOUNCES ||
+        (o.accumulate != 0 && o.accumulate != 1)) {
+        rt_set_error("rt_trace_paths: samples %d (0 .. 2^20), max_depth %d (0 .. 2^24 - 1) or accumulate %d (0 / 1)",
+                     o.samples, o.max_depth, o.accumulate);
+        return RT_E_INVALID;
+    }
+    if (o.traversal != RT_TRAVERSAL_BOUNDED && o.traversal != RT_TRAVERSAL_KD &&
+        o.traversal != RT_TRAVERSAL_BOUNDED_COUNTED) {
+        rt_set_error("rt_trace_paths: traversal %d", o.traversal);
+        return RT_E_INVALID;
+    }
+    if (n == 0) return RT_OK;
+    if (scene->max_depth > RT_STACK_DEPTH) {
+        rt_set_error("rt_trace_paths: KD tree depth %d beyond the traversal stack (%d)", scene->max_depth, RT_STACK_DEPTH);
+        return RT_E_UNSUPPORTED;
+    }
+    rt_register_shutdown();
+    hipStream_t stream = (hipStream_t)o.stream;
+    if (rt_launch_trace_paths(scene->dev, rays, rng, n, radiance, sq_luminance, o.samples ? o.samples : 1, o.max_depth,
+                              o.accumulate, o.traversal, o.stats_device, stream) != 0) {
+        rt_set_error("rt_trace_paths: launch failed: %s", hipGetErrorString(hipGetLastError()));
         return RT_E_HIP;
     }
     if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));

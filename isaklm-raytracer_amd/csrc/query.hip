@@ -1,6 +1,6 @@
 // query.hip — the batched ray query (rt_trace_rays), the occlusion query
-// (rt_occluded), the camera-ray generator (rt_camera_rays) and the first-hit
-// AOV pass (rt_render_aov).
+// (rt_occluded), the radiance query (rt_trace_paths), the camera-ray generator
+// (rt_camera_rays) and the first-hit AOV pass (rt_render_aov).
 //
 // The closest-hit query is the renderer's own: trace_ray (rt/trace_ray.cuh:
 // 244-318) as rt_kernels.h trace() restates it, sped up by the conservative
@@ -12,6 +12,8 @@
 //   rt_render_aov   rays from the camera    -> planar AOV buffers
 // and a second kernel of the same shape for the any-hit question:
 //   rt_occluded     rays + tmax from buffers -> one byte per ray
+// and a third that runs the renderer's whole path loop on the caller's rays:
+//   rt_trace_paths  rays + RNG states        -> summed radiance per ray
 //
 // One ray per lane; the lanes of a wave take their next rays together from a
 // global counter (one wave-aggregated atomic per round).  The traversal stack
@@ -41,6 +43,12 @@
 #endif
 #ifndef RQ_WAVES
 #define RQ_WAVES 4 // waves per SIMD = resident blocks per CU
+#endif
+#ifndef PQ_LDS
+#define PQ_LDS 10 // rt_path_query_kernel: as RQ_LDS (the shared spill area holds the entries past RQ_LDS)
+#endif
+#ifndef PQ_WAVES
+#define PQ_WAVES 4 // rt_path_query_kernel: resident blocks per CU (<= RQ_WAVES: the spill area's threads)
 #endif
 #ifndef RQ_COUNT_EARLY
 #define RQ_COUNT_EARLY 0 // 1: rt_occluded's stats get a fourth word (a counting build, never the shipped one)
@@ -142,6 +150,13 @@ __device__ __forceinline__ bool direction_in_domain(Vec3D d)
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum64(uint32_t lane_count)
+{
+    unsigned long long v = lane_count;
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
@@ -303,6 +318,189 @@ __global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
     }
 }
 
+// ---- the radiance query (rt_trace_paths) ----
+// trace_path (rt/path_tracing.cuh:268-325) for the caller's rays: ray e is
+// traced `samples` times from rng[e], started as the renderer starts a camera
+// ray (PRIMARY, outside every medium, throughput 1), and the sums of L and of
+// luminance(L)^2 (:322-324) go to radiance[e] / sq[e], the RNG state back to
+// rng[e].  The loop is rt_path_kernel's (path_kernel.hip): one ray query per
+// iteration from one place, extension and NEE shadow rays as two states of
+// it, the path state in registers.
+//
+// Regeneration is per lane: a lane whose path ends starts its ray's next
+// sample in the same iteration, and a lane whose ray is done stores it and
+// takes the next ray index from the launch's counter — one atomic for the
+// lanes of the wave that need a ray in that iteration.  (Path lengths run
+// from 1 to ~10^4 extension rays in glass: a refill in lockstep, as
+// rt_query_kernel's, would hold 63 lanes for the longest path of every
+// round.)  A lane leaves when the counter is past n.
+//
+// The gate is applied to every query: the caller's ray may be any 6 floats;
+// the rays scatter() and NEE make are unit directions and pass its first part.
+// stats (optional) adds [0] rays, [1] paths, [2] trace_ray calls, [3] paths
+// cut at `limit`; [4] is the longest path (a maximum).  The per-lane counts
+// are 32-bit: a lane makes fewer than 2^32 queries in any launch that ends.
+__global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
+    rt_path_query_kernel(RtDevScene sc, BufferRays src, uint32_t *rng_io, float *radiance, float *sq_out, uint32_t n,
+                         int samples, int limit, int accumulate, int kd_only, uint32_t *fetch,
+                         unsigned long long *stats, uint2 *spill, int spill_threads)
+{
+    __shared__ uint32_t s_node[PQ_LDS * RQ_BLOCK];
+    __shared__ float s_entry[PQ_LDS * RQ_BLOCK];
+    const int tid = threadIdx.x;
+    const int gtid = blockIdx.x * RQ_BLOCK + tid;
+    Stack<PQ_LDS> stk{s_node + tid, s_entry + tid, RQ_BLOCK, spill + gtid, spill_threads};
+    Cnt c; // (never counted)
+    const int lane = __lane_id();
+    uint32_t n_rays = 0, n_paths = 0, n_trace = 0, n_cut = 0, max_len = 0;
+
+    uint32_t e = 0, rng = 0;
+    bool have_ray = false, have_path = false;
+    int samples_left = 0;
+    Vec3D o0 = rt_v3(0, 0, 0), d0 = rt_v3(0, 0, 0); // the caller's ray
+    Vec3D sum = rt_v3(0, 0, 0);
+    float sum_sq = 0.0f;
+
+    bool shadow = false; // current query is an NEE shadow ray
+    bool inside = false; // inside_medium
+    int prev_type = PRIMARY;
+    int depth = 0;
+    int light = 0;
+    Vec3D ro = rt_v3(0, 0, 0), rd = rt_v3(0, 0, 0); // ray being traced
+    Vec3D cont = rt_v3(0, 0, 0);                     // scattered direction waiting behind a shadow ray
+    Vec3D sn_normal = rt_v3(0, 0, 0), rp = rt_v3(0, 0, 0);
+    Vec3D T = rt_v3(1, 1, 1), L = rt_v3(0, 0, 0);
+
+    while (true) {
+        if (!have_path) {
+            if (samples_left == 0) {
+                if (have_ray) { // the finished ray's records
+                    float *r = radiance + 3 * (size_t)e;
+                    r[0] = sum.x;
+                    r[1] = sum.y;
+                    r[2] = sum.z;
+                    if (sq_out) sq_out[e] = sum_sq;
+                    rng_io[e] = rng;
+                    have_ray = false;
+                }
+                // the next ray, for the lanes that are here
+                const unsigned long long m = __ballot(true);
+                const int leader = __ffsll((long long)m) - 1;
+                uint32_t base = 0;
+                if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
+                base = __shfl(base, leader);
+                e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                if (e >= n) break; // (the counter stops below n + the grid's threads <= 2^31 + 2^20: no wrap)
+                src.load(e, o0, d0);
+                rng = rng_io[e];
+                sum = rt_v3(0.0f, 0.0f, 0.0f);
+                sum_sq = 0.0f;
+                if (accumulate) {
+                    const float *r = radiance + 3 * (size_t)e;
+                    sum = rt_v3(r[0], r[1], r[2]);
+                    if (sq_out) sum_sq = sq_out[e];
+                }
+                have_ray = true;
+                samples_left = samples;
+                ++n_rays;
+            }
+            --samples_left;
+            ro = o0;
+            rd = d0;
+            T = rt_v3(1.0f, 1.0f, 1.0f);
+            L = rt_v3(0.0f, 0.0f, 0.0f);
+            inside = false;
+            prev_type = PRIMARY;
+            depth = 0;
+            shadow = false;
+            have_path = true;
+            ++n_paths;
+        }
+
+        bool finish = false;
+        if (!shadow && depth == limit) { // max_depth / watchdog
+            ++n_cut;
+            finish = true;
+        } else {
+            if (!shadow) ++depth;
+            ++n_trace;
+            float bx = 0.0f, by = 0.0f, bz = 0.0f;
+            int hit;
+            // the domain gate (see the head of this file)
+            if (!kd_only && direction_in_domain(rd) && rt_bounded_ray(ro, rd, sc.split_vals, sc.split_off))
+                hit = trace_bvh<false>(sc, ro, rd, bx, by, bz, stk, c);
+            else
+                hit = trace<false>(sc, ro, rd, bx, by, bz, stk, c);
+            bool roulette = true;
+            if (!shadow) {
+                if (hit < 0) {
+                    finish = true; // miss: break without roulette (:303-306)
+                    roulette = false;
+                } else {
+                    Surface s;
+                    shade<false>(sc, hit, bx, by, bz, rd, s, c);
+                    if (prev_type != DIFFUSE) L = L + s.emittance * T; // :285-288
+                    Vec3D nd, w;
+                    prev_type = scatter(rd, inside, rng, s, nd, w);
+                    T = T * w;
+                    ro = s.position;
+                    rd = nd;
+                    if (prev_type == DIFFUSE) { // sample_direct_light (:235-265)
+                        float xi = rng_next(rng);
+                        if (sc.light_count == 0) {
+                            rng_next(rng);
+                            rng_next(rng);
+                            L = L + rt_v3(0.0f, 0.0f, 0.0f) * T;
+                        } else {
+                            light = sc.lights[(int)(xi * (float)sc.light_count)];
+                            rp = light_point(sc, light, rng);
+                            cont = rd;
+                            sn_normal = s.normal;
+                            rd = rt_normalize(rp - ro);
+                            shadow = true;
+                            roulette = false; // roulette after the shadow ray
+                        }
+                    }
+                }
+            } else {
+                Vec3D direct = rt_v3(0.0f, 0.0f, 0.0f);
+                if (hit >= 0 && hit == light) direct = light_contribution(sc, light, bx, by, bz, ro, rd, rp, sn_normal);
+                L = L + direct * T;
+                rd = cont;
+                shadow = false;
+            }
+            if (roulette) { // Russian roulette (:309-318)
+                float p = fmaxf(T.x, fmaxf(T.y, T.z));
+                float r = rng_next(rng);
+                if (r > p) finish = true;
+                else T = T * (1.0f / p);
+            }
+        }
+        if (finish) { // accumulation (:322-324)
+            sum = sum + L;
+            sum_sq = sum_sq + rt_square(rt_luminance(L));
+            max_len = (uint32_t)depth > max_len ? (uint32_t)depth : max_len;
+            have_path = false;
+        }
+    }
+
+    if (stats) { // (every lane of the wave is here: the loop's exits reconverge)
+        const unsigned long long rays = wave_sum64(n_rays), paths = wave_sum64(n_paths), calls = wave_sum64(n_trace),
+                                 cuts = wave_sum64(n_cut);
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t other = __shfl_xor(max_len, off);
+            max_len = other > max_len ? other : max_len;
+        }
+        if (lane == 0) {
+            if (rays) atomicAdd(stats + 0, rays);
+            if (paths) atomicAdd(stats + 1, paths);
+            if (calls) atomicAdd(stats + 2, calls);
+            if (cuts) atomicAdd(stats + 3, cuts);
+            if (max_len) atomicMax(stats + 4, (unsigned long long)max_len);
+        }
+    }
+}
+
 // rt_camera_rays: ray y*W + x = the centre of pixel (x, y), three 8-B stores per lane
 __global__ void __launch_bounds__(RQ_BLOCK) rt_camera_rays_kernel(CameraRays src, float2 *rays, uint32_t n)
 {
@@ -341,13 +539,13 @@ constexpr int kSpillDepth = (RT_BVH_STACK > RT_STACK_DEPTH ? RT_BVH_STACK : RT_S
 template <typename SRC, typename SINK>
 using QueryKernel = void (*)(RtDevScene, SRC, SINK, uint32_t, int, uint32_t *, unsigned long long *, uint2 *, int);
 
-template <typename SRC, typename SINK>
-int launch_query(QueryKernel<SRC, SINK> kernel, const RtDevScene &sc, const SRC &src, const SINK &sink, long long n, int traversal,
-                 unsigned long long *stats, hipStream_t stream)
+// The device's workspace, made on first use, with `stream` waiting for the
+// previous launch that used it and the ray counter zeroed on `stream`
+// (g_query_mu is held by the caller until query_launched); nullptr on error.
+QueryWorkspace *query_workspace(hipStream_t stream)
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    std::lock_guard<std::mutex> g(g_query_mu);
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     QueryWorkspace &w = g_query[dev];
     if (!w.blocks) {
         hipDeviceProp_t prop;
@@ -356,29 +554,54 @@ int launch_query(QueryKernel<SRC, SINK> kernel, const RtDevScene &sc, const SRC 
                             : 256;
         w.blocks = cus * RQ_WAVES;
     }
-    if (!w.last && hipEventCreateWithFlags(&w.last, hipEventDisableTiming) != hipSuccess) return -1;
+    if (!w.last && hipEventCreateWithFlags(&w.last, hipEventDisableTiming) != hipSuccess) return nullptr;
     if (!w.fetch) {
         void *p = nullptr;
-        if (hipMalloc(&p, 64) != hipSuccess) return -1;
+        if (hipMalloc(&p, 64) != hipSuccess) return nullptr;
         w.fetch = (uint32_t *)p;
     }
     const size_t threads = (size_t)w.blocks * RQ_BLOCK;
     if (!w.spill) {
         void *p = nullptr;
-        if (hipMalloc(&p, threads * (size_t)kSpillDepth * sizeof(uint2)) != hipSuccess) return -1;
+        if (hipMalloc(&p, threads * (size_t)kSpillDepth * sizeof(uint2)) != hipSuccess) return nullptr;
         w.spill = (uint2 *)p;
         w.spill_threads = threads;
     }
-    if (w.recorded && hipStreamWaitEvent(stream, w.last, 0) != hipSuccess) return -1;
-    if (hipMemsetAsync(w.fetch, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
+    if (w.recorded && hipStreamWaitEvent(stream, w.last, 0) != hipSuccess) return nullptr;
+    if (hipMemsetAsync(w.fetch, 0, sizeof(uint32_t), stream) != hipSuccess) return nullptr;
+    return &w;
+}
+
+// the resident grid for n rays at `per_cu` blocks per CU (<= RQ_WAVES: the spill area has w.blocks blocks' slots)
+int query_grid(const QueryWorkspace &w, long long n, int per_cu)
+{
     const long long need = (n + RQ_BLOCK - 1) / RQ_BLOCK;
-    const int grid = (int)(need < (long long)w.blocks ? need : (long long)w.blocks);
-    const int kd_only = traversal == RT_TRAVERSAL_KD || sc.bvh_nodes == nullptr || sc.bvh4 == nullptr;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(RQ_BLOCK), 0, stream, sc, src, sink, (uint32_t)n, kd_only, w.fetch, stats,
-                       w.spill, (int)w.spill_threads);
+    const long long resident = (long long)(w.blocks / RQ_WAVES) * per_cu;
+    return (int)(need < resident ? need : resident);
+}
+
+int query_launched(QueryWorkspace &w, hipStream_t stream)
+{
     if (hipGetLastError() != hipSuccess || hipEventRecord(w.last, stream) != hipSuccess) return -1;
     w.recorded = true;
     return 0;
+}
+
+bool query_kd_only(const RtDevScene &sc, int traversal)
+{
+    return traversal == RT_TRAVERSAL_KD || sc.bvh_nodes == nullptr || sc.bvh4 == nullptr;
+}
+
+template <typename SRC, typename SINK>
+int launch_query(QueryKernel<SRC, SINK> kernel, const RtDevScene &sc, const SRC &src, const SINK &sink, long long n, int traversal,
+                 unsigned long long *stats, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> g(g_query_mu);
+    QueryWorkspace *w = query_workspace(stream);
+    if (!w) return -1;
+    hipLaunchKernelGGL(kernel, dim3(query_grid(*w, n, RQ_WAVES)), dim3(RQ_BLOCK), 0, stream, sc, src, sink, (uint32_t)n,
+                       (int)query_kd_only(sc, traversal), w->fetch, stats, w->spill, (int)w->spill_threads);
+    return query_launched(*w, stream);
 }
 
 CameraRays camera_source(const RtDevCamera &cam, int width, int height)
@@ -408,6 +631,21 @@ int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tma
     const BufferRaysTmax src{BufferRays{reinterpret_cast<const float2 *>(rays)}, tmax};
     const ByteSink sink{occluded};
     return launch_query(rt_occluded_kernel<BufferRaysTmax, ByteSink>, sc, src, sink, n, traversal, stats, stream);
+}
+
+int rt_launch_trace_paths(const RtDevScene &sc, const float *rays, uint32_t *rng, long long n, float *radiance, float *sq,
+                          int samples, int max_depth, int accumulate, int traversal, unsigned long long *stats,
+                          hipStream_t stream)
+{
+    static_assert(PQ_WAVES <= RQ_WAVES && PQ_LDS >= RQ_LDS, "rt_path_query_kernel within the shared spill area");
+    const BufferRays src{reinterpret_cast<const float2 *>(rays)};
+    std::lock_guard<std::mutex> g(g_query_mu);
+    QueryWorkspace *w = query_workspace(stream);
+    if (!w) return -1;
+    hipLaunchKernelGGL(rt_path_query_kernel, dim3(query_grid(*w, n, PQ_WAVES)), dim3(RQ_BLOCK), 0, stream, sc, src, rng,
+                       radiance, sq, (uint32_t)n, samples, max_depth > 0 ? max_depth : RT_WATCHDOG_BOUNCES, accumulate,
+                       (int)query_kd_only(sc, traversal), w->fetch, stats, w->spill, (int)w->spill_threads);
+    return query_launched(*w, stream);
 }
 
 int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width, int height, float *depth,

@@ -71,6 +71,11 @@ class RtQueryOptions(ctypes.Structure):
     _fields_ = [("traversal", ctypes.c_int), ("stream", ctypes.c_void_p), ("stats_device", ctypes.c_void_p)]
 
 
+class RtPathOptions(ctypes.Structure):
+    _fields_ = [("samples", ctypes.c_int), ("max_depth", ctypes.c_int), ("accumulate", ctypes.c_int),
+                ("traversal", ctypes.c_int), ("stream", ctypes.c_void_p), ("stats_device", ctypes.c_void_p)]
+
+
 class RtAovBuffers(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
                 ("triangle", ctypes.c_void_p)]
@@ -225,6 +230,9 @@ def lib():
         L.rt_default_query_options.restype = None
         L.rt_trace_rays.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, ctypes.POINTER(RtQueryOptions)]
         L.rt_occluded.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, ctypes.POINTER(RtQueryOptions)]
+        L.rt_default_path_options.argtypes = [ctypes.POINTER(RtPathOptions)]
+        L.rt_default_path_options.restype = None
+        L.rt_trace_paths.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.POINTER(RtPathOptions)]
         L.rt_camera_rays.argtypes = [Camera, i, i, vp, vp]
         L.rt_render_aov.argtypes = [vp, Camera, i, i, ctypes.POINTER(RtAovBuffers), ctypes.POINTER(RtQueryOptions)]
         L.rt_default_denoise_options.argtypes = [ctypes.POINTER(RtDenoiseOptions)]
@@ -592,6 +600,82 @@ def occluded(dscene, rays, tmax=None, traversal=None, stream=None, stats=False):
         if stats:
             check(L.rt_download(_ptr(st), d_st, st.nbytes))
     return (out, dict(zip(OCCLUSION_STATS, (int(v) for v in st)))) if stats else out
+
+
+PATH_STATS = ("rays", "paths", "trace_calls", "cut_paths", "max_depth")  # RtPathOptions.stats_device [0..4]
+
+
+def path_options(samples=1, max_depth=0, accumulate=False, traversal=None, stream=None, stats=None):
+    """RtPathOptions; samples: paths per ray; max_depth: 0 = unbounded, else the most extension rays of a path;
+    accumulate: add to what the output buffers hold; traversal, stream as query_options; stats: a device
+    pointer to 5 u64 (PATH_STATS: the call adds to the first four, the fifth is a maximum)."""
+    o = RtPathOptions()
+    lib().rt_default_path_options(ctypes.byref(o))
+    o.samples, o.max_depth, o.accumulate = int(samples), int(max_depth), int(accumulate)
+    if traversal is not None:
+        o.traversal = traversal
+    o.stream = stream
+    o.stats_device = stats
+    return o
+
+
+def trace_paths_device(dscene, rays_ptr, rng_ptr, n, radiance_ptr, sq_ptr=None, samples=1, max_depth=0,
+                       accumulate=False, traversal=None, stream=None, stats_ptr=None):
+    """rt_trace_paths on device memory: integer device pointers (a torch tensor's data_ptr()) to n x 6 float32
+    rays, n uint32 RNG states (read and written), n x 3 float32 radiance sums and optionally n float32 sums of
+    squared luminance; stream: an integer hipStream_t (torch.cuda.current_stream().cuda_stream) — the call is
+    then only enqueued."""
+    o = path_options(samples, max_depth, accumulate, traversal, stream, _int_ptr(stats_ptr))
+    check(lib().rt_trace_paths(dscene.prepared, _int_ptr(rays_ptr), _int_ptr(rng_ptr), int(n), _int_ptr(radiance_ptr),
+                               _int_ptr(sq_ptr), ctypes.byref(o)))
+
+
+def trace_paths(dscene, rays, rng, samples=1, max_depth=0, traversal=None, stream=None, stats=False, radiance=None,
+                sq=None):
+    """Path-traced radiance along `rays` — a numpy (n, 6) float32 array as for trace_rays — `samples` paths
+    each, from the (n,) uint32 RNG states `rng`: the reference's trace_path, bit for bit.  Returns (radiance
+    (n, 3) float32, sq (n,) float32, rng_out (n,) uint32): the SUMS of L and of luminance(L)^2 over the samples
+    and the RNG states after them; with stats=True also a dict of the call's counts (PATH_STATS).  Passing
+    `radiance` (and `sq`) arrays of an earlier call accumulates onto them (they are not modified)."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must have shape (n, 6)")
+    n = len(rays)
+    rng = np.asarray(rng)
+    if rng.dtype != np.uint32 or rng.shape != (n,):
+        raise ValueError("rng must be a uint32 array of shape (n,)")
+    if radiance is None and sq is not None:
+        raise ValueError("sq without radiance: pass both arrays of the earlier call to accumulate")
+    for name, a, shape in (("radiance", radiance, (n, 3)), ("sq", sq, (n,))):
+        if a is not None and (np.asarray(a).dtype != np.float32 or np.asarray(a).shape != shape):
+            raise ValueError(f"{name} must be a float32 array of shape {shape}")
+    accumulate = radiance is not None
+    rng = np.ascontiguousarray(rng).copy()
+    rad = np.ascontiguousarray(radiance).copy() if accumulate else np.zeros((n, 3), np.float32)
+    sqv = np.ascontiguousarray(sq).copy() if sq is not None else np.zeros(n, np.float32)
+    L = lib()
+    st = np.zeros(5, dtype=np.uint64)
+    with _DeviceBytes(rays.nbytes) as d_rays, _DeviceBytes(rng.nbytes) as d_rng, _DeviceBytes(rad.nbytes) as d_rad, \
+            _DeviceBytes(sqv.nbytes) as d_sq, _DeviceBytes(st.nbytes) as d_st:
+        if n:
+            check(L.rt_upload(d_rays, _ptr(rays), rays.nbytes))
+            check(L.rt_upload(d_rng, _ptr(rng), rng.nbytes))
+            if accumulate:
+                check(L.rt_upload(d_rad, _ptr(rad), rad.nbytes))
+                check(L.rt_upload(d_sq, _ptr(sqv), sqv.nbytes))
+        if stats:
+            check(L.rt_memset(d_st, 0, st.nbytes))
+        trace_paths_device(dscene, d_rays, d_rng, n, d_rad, d_sq, samples, max_depth, accumulate, traversal, stream,
+                           d_st if stats else None)
+        _synchronize_stream(stream)
+        if n:
+            check(L.rt_download(_ptr(rad), d_rad, rad.nbytes))
+            check(L.rt_download(_ptr(sqv), d_sq, sqv.nbytes))
+            check(L.rt_download(_ptr(rng), d_rng, rng.nbytes))
+        if stats:
+            check(L.rt_download(_ptr(st), d_st, st.nbytes))
+    out = (rad, sqv, rng)
+    return out + (dict(zip(PATH_STATS, (int(v) for v in st))),) if stats else out
 
 
 def camera_rays(camera, width, height):
