@@ -614,6 +614,16 @@ typedef struct RtDeviations {
     unsigned long long wide_overflows;
 } RtDeviations;
 int rt_deviation_stats(RtDeviations *out, int reset);
+/* The T* certificate of the bounded traversal (added within ABI 12; counting
+ * renders only: RtOptions.traversal = RT_TRAVERSAL_BOUNDED_COUNTED on the
+ * wavefront kernel): of the rays that hit something, how many the
+ * certificate covered (no KD descent) and how many a KD descent found
+ * (rays it does not cover, and the few the bound does not apply to); their
+ * sum is RT_CNT_HIT.  On this device since the last reset (rt_deviation_stats' reset
+ * zeroes them too).  Either pointer may be NULL.  Joins like
+ * rt_deviation_stats. */
+#define RT_HAS_KD_CERT_STATS 1
+int rt_kd_cert_stats(unsigned long long *certified, unsigned long long *fallback, int reset);
 
 void rt_default_options(RtOptions *opt);
 /* render(): if sample_count == 0 the frame's fb/sq/count are reset first

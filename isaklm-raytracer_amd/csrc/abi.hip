@@ -169,6 +169,18 @@ int upload_prepared(const rt_host::PreparedHost &h, int ntris, int nindices, rt_
         return rc;
     }
     if (dv.kd_cell) dv.kd_grid = h.kd_grid;
+    // the T* certificate's tables (bvh_common.h rt_kd_cert)
+    dv.kd_cert = RtKdCert{nullptr, nullptr, {0, 0, 0}, {31, 31, 31}, h.bvh_scale};
+    if (h.bvh_depth >= 0 && !h.kd_safe.empty()) {
+        if ((rc = upload_vec(*s, h.kd_safe, &dv.kd_cert.safe)) || (rc = upload_vec(*s, h.split_hash, &dv.kd_cert.hash))) {
+            release(s);
+            return rc;
+        }
+        for (int a = 0; a < 3; ++a) {
+            dv.kd_cert.hoff[a] = h.split_hoff[a];
+            dv.kd_cert.hshift[a] = h.split_hshift[a];
+        }
+    }
     dv.nodes = nodes;
     dv.isect_a = a;
     dv.isect_bary = bary;
@@ -281,6 +293,22 @@ int rt_deviation_stats(RtDeviations *out, int reset)
     out->long_closed = w[RT_DEV_LONG_CLOSED];
     out->wide_overflows = w[RT_DEV_WIDE_OVERFLOW];
     if (reset) HIPCHK(hipMemset(d, 0, RT_DEV_WORDS * 8));
+    return RT_OK;
+}
+
+// the T* certificate's counters of counting renders (RT_DEV_CERT_*; zeroed by rt_deviation_stats' reset too)
+int rt_kd_cert_stats(unsigned long long *certified, unsigned long long *fallback, int reset)
+{
+    unsigned long long *d = dev_stats_block();
+    if (!d) { rt_set_error("rt_kd_cert_stats: no device block"); return RT_E_HIP; }
+    const int jr = join_status(nullptr, "rt_kd_cert_stats", 0);
+    if (jr != RT_OK && jr != RT_E_INCOMPLETE) return jr;
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long w[2];
+    HIPCHK(hipMemcpy(w, d + RT_DEV_CERT_OK, sizeof w, hipMemcpyDeviceToHost));
+    if (certified) *certified = w[0];
+    if (fallback) *fallback = w[1];
+    if (reset) HIPCHK(hipMemset(d + RT_DEV_CERT_OK, 0, sizeof w));
     return RT_OK;
 }
 

@@ -113,3 +113,79 @@ RT_HD bool rt_tri_bary(RtF4 B, RtF4 C, RtF4 D, float rd, Vec3D o, Vec3D d, float
     cx = 1.0f - cy - cz;
     return rt_bary_inside(cx, cy, cz);
 }
+
+// ---- the T* certificate (DESIGN.md §5 "The certificate") ----
+// After the s_min query, T* (BVH slot tk, whose test alone set s_min) is the
+// bounded traversal's result wherever the first KD leaf with entry <= s_min <
+// exit lists it.  rt_kd_cert proves that from two host tables instead of
+// walking the tree: the per-slot safe box (every KD leaf whose closed cell
+// meets it lists the slot's triangle: host/scene_prepare.cpp build_kd_cert)
+// and the per-axis hash sets of the split values.  Host and device run this
+// same code (tests/native/kd_cert_check.cpp).
+#ifndef RT_KD_CERT
+#define RT_KD_CERT 1 // 0 (a HIP compile flag, for A/B): every ray runs the KD descent (kd_bounded), as before the
+                     // certificate.  The kernels' switch only: scene preparation (host code) still builds and uploads
+                     // the tables, so set-up time and scene bytes stay those of the certificate build
+#endif
+#define RT_SPLIT_EMPTY 0x7FC00001u // an unused hash slot (a NaN: no split value — scene_prepare drops the bound then)
+#define RT_SPLIT_BUCKETS 2         // 4-slot buckets read per lookup; a run that has not ended by then counts as "member"
+// why a ray is not certified (0: it is)
+#define RT_CERT_OK 0
+#define RT_CERT_TIE 1      // no single slot has s_min (RT_TK_TIE)
+#define RT_CERT_INTERVAL 2 // not entry <= s_min < the root's exit
+#define RT_CERT_DIR 3      // a direction component of 2 or more (a split distance could underflow to 0)
+#define RT_CERT_ORIGIN 4   // an origin coordinate is a split value on an axis the ray goes up
+#define RT_CERT_BOX 5      // the hit point is not delta inside the slot's safe box
+
+RT_HD uint32_t rt_float_bits(float f)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    return u;
+}
+
+// Whether v is in the open-addressing set tab[0, 2^(32 - shift)) (keys = the bits of v + 0: -0 is +0).
+// A key sits in the first free slot at or after the start of its home bucket (4 slots, 16-B aligned:
+// one load), so a bucket without the key that still has a free slot ends the search.  Never a false
+// "no"; a false "yes" (both buckets full of other keys) only sends a ray to the descent.
+RT_HD bool rt_split_member(const uint32_t *tab, int shift, float v)
+{
+    const uint32_t key = rt_float_bits(v + 0.0f);
+    const uint32_t mask = (1u << (32 - shift)) - 1u;
+    uint32_t i = ((key * 0x9E3779B1u) >> shift) & ~3u;
+    for (int k = 0; k < RT_SPLIT_BUCKETS; ++k) {
+        uint32_t w[4];
+        __builtin_memcpy(w, __builtin_assume_aligned(tab + i, 16), 16);
+        if (w[0] == key || w[1] == key || w[2] == key || w[3] == key) return true;
+        if (w[0] == RT_SPLIT_EMPTY || w[1] == RT_SPLIT_EMPTY || w[2] == RT_SPLIT_EMPTY || w[3] == RT_SPLIT_EMPTY)
+            return false;
+        i = (i + 4u) & mask;
+    }
+    return true;
+}
+
+// the certificate's per-ray slack: >= 4x the derived e_P + delta_desc, in the form of rt_ray_margin
+RT_HD float rt_cert_delta(Vec3D o, float scale)
+{
+    return 0x1p-19f * (fabsf(o.x) + fabsf(o.y) + fabsf(o.z) + 2.0f * scale);
+}
+
+// RT_CERT_OK when kd_bounded(o, d, entry, root_exit, s_min, T* of tk) provably returns T*'s own test
+// (for a ray rt_bounded_ray admits).  X: the point fl(o + fl(d * s_min)) (rt_tri_bary's).
+RT_HD int rt_kd_cert(const RtKdCert &kc, Vec3D o, Vec3D d, float entry, float root_exit, float s_min, int tk)
+{
+    if (tk < 0) return RT_CERT_TIE;
+    if (!(entry <= s_min && s_min < root_exit)) return RT_CERT_INTERVAL;
+    if (!(fabsf(d.x) < 2.0f && fabsf(d.y) < 2.0f && fabsf(d.z) < 2.0f)) return RT_CERT_DIR;
+    const RtF4 lo = kc.safe[2 * (size_t)tk], hi = kc.safe[2 * (size_t)tk + 1];
+    const float dl = rt_cert_delta(o, kc.scale);
+    const float px = o.x + d.x * s_min, py = o.y + d.y * s_min, pz = o.z + d.z * s_min;
+    if (!(lo.x + dl <= px && px <= hi.x - dl && lo.y + dl <= py && py <= hi.y - dl && lo.z + dl <= pz &&
+          pz <= hi.z - dl))
+        return RT_CERT_BOX;
+    if ((d.x > 0.0f && rt_split_member(kc.hash + kc.hoff[0], kc.hshift[0], o.x)) ||
+        (d.y > 0.0f && rt_split_member(kc.hash + kc.hoff[1], kc.hshift[1], o.y)) ||
+        (d.z > 0.0f && rt_split_member(kc.hash + kc.hoff[2], kc.hshift[2], o.z)))
+        return RT_CERT_ORIGIN;
+    return RT_CERT_OK;
+}

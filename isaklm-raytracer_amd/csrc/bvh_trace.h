@@ -313,15 +313,58 @@ __device__ __forceinline__ bool bvh4_query(const RtDevScene &sc, Vec3D o, Vec3D 
     return true;
 }
 
-// (tstar: the triangle whose test alone set s_min — kd_bounded's fast leaf —, else -1)
+// (tstar: the triangle whose test alone set s_min — kd_bounded's fast leaf —, else -1; tk: its BVH slot,
+// -1 / RT_TK_TIE as leaf_scan_min leaves it)
+template <bool COUNT, typename STACK>
+__device__ __forceinline__ float bvh4_bound(const RtDevScene &sc, Vec3D o, Vec3D d, float best, STACK &stk, Cnt &cn,
+                                            int &tstar, int &tk)
+{
+    BvhPark pk;
+    (void)bvh4_query<COUNT, false>(sc, o, d, best, stk, cn, 0, false, pk);
+    tk = pk.tk;
+    tstar = pk.tk >= 0 ? (int)sc.bvh_bary[pk.tk].tri : -1;
+    return pk.best;
+}
 template <bool COUNT, typename STACK>
 __device__ __forceinline__ float bvh4_bound(const RtDevScene &sc, Vec3D o, Vec3D d, float best, STACK &stk, Cnt &cn,
                                             int &tstar)
 {
-    BvhPark pk;
-    (void)bvh4_query<COUNT, false>(sc, o, d, best, stk, cn, 0, false, pk);
-    tstar = pk.tk >= 0 ? (int)sc.bvh_bary[pk.tk].tri : -1;
-    return pk.best;
+    int tk;
+    return bvh4_bound<COUNT>(sc, o, d, best, stk, cn, tstar, tk);
+}
+
+// The T* certificate (bvh_common.h rt_kd_cert): where it holds, step 3's descent would end in
+// a leaf that lists T* and return T*'s own test — the triangle of BVH slot tk with the barycentrics of
+// rt_tri_bary on that slot's record at s = s_min (the s its rt_tri_plane gave the query: leaf_scan_min),
+// the same arithmetic on the same floats as kd_bounded's T* leaf runs on the KD entry's copy.  True: the
+// hit is set (RT_CNT_HIT counted where `count`); false: the caller runs the descent.  COUNT: c.cert[0] counts
+// the certified rays; the callers count in c.cert[1] the hits found by a KD descent instead — rays the certificate
+// did not cover and rays the bound does not apply to —, so cert[0] + cert[1] = RT_CNT_HIT.  (A few descents of
+// bounded rays miss although a test passes: the reference's split-at-the-origin quirk)
+template <bool COUNT>
+__device__ __forceinline__ bool kd_certified(const RtDevScene &sc, const Vec3D o, const Vec3D d, const float entry,
+                                             const float root_exit, const float s_min, const int tk, int &hit,
+                                             float &hbx, float &hby, float &hbz, Cnt &c, const bool count = true)
+{
+#if RT_KD_CERT
+    if (!sc.kd_cert.safe) return false;
+    if (rt_kd_cert(sc.kd_cert, o, d, entry, root_exit, s_min, tk) != RT_CERT_OK) return false;
+    const RtIsectBary *r = sc.bvh_bary + tk;
+    float cx, cy, cz;
+    if (!rt_tri_bary(ldc4(&r->b), ldc4(&r->c), ldc4(&r->d), ldc_f(&r->rd), o, d, s_min, cx, cy, cz))
+        return false; // (never: this test passed in the query)
+    if (COUNT && count) {
+        c.v[RT_CNT_HIT]++;
+        c.cert[0]++;
+    }
+    hit = (int)ldc_u2(&r->rd).y;
+    hbx = cx;
+    hby = cy;
+    hbz = cz;
+    return true;
+#else
+    return false;
+#endif
 }
 
 // step 3: the reference's KD traversal with the skip bound s_min (-inf: the
@@ -439,35 +482,52 @@ __device__ __forceinline__ int trace_bvh(const RtDevScene &sc, const Vec3D o, co
     float s_min = -INFINITY; // (the plain KD traversal)
     int tstar = -1;
     if (rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
-        s_min = RT_BVH4 ? bvh4_bound<COUNT>(sc, o, d, exit_, stk, c, tstar) : bvh_bound<COUNT>(sc, o, d, exit_, stk, c);
+        int tk = -1;
+        s_min = RT_BVH4 ? bvh4_bound<COUNT>(sc, o, d, exit_, stk, c, tstar, tk)
+                        : bvh_bound<COUNT>(sc, o, d, exit_, stk, c);
         if (!(s_min < root_exit)) return -1;
+        int hit;
+        if (kd_certified<COUNT>(sc, o, d, entry, root_exit, s_min, tk, hit, hbx, hby, hbz, c)) return hit;
     }
-    return kd_bounded<COUNT>(sc, o, d, entry, root_exit, s_min, tstar, hbx, hby, hbz, stk, c);
+    const int h = kd_bounded<COUNT>(sc, o, d, entry, root_exit, s_min, tstar, hbx, hby, hbz, stk, c);
+    if (COUNT && h >= 0) c.cert[1]++;
+    return h;
 }
 
-// trace_bvh with the s_min query parked after `cap` node steps (bvh4_query):
-// false = parked (pk holds the query's state; call again with resume), true =
-// done with the hit in `hit` (-1: miss) — trace_bvh's result, bit for bit
+// trace_bvh with the s_min query parked after `cap` node steps (bvh4_query), and with the KD descent of
+// a ray the certificate does not cover put off where the caller asks (defer_kd).  Returns RT_PARK_DONE
+// with the hit in `hit` (-1: miss) — trace_bvh's result, bit for bit —, RT_PARK_BVH (pk holds the query's
+// state) or RT_PARK_KD (pk.best / pk.tk hold s_min and its slot: only the descent is left); call again
+// with that value as `resume`.  Lanes are independent paths: any schedule gives the same bits.
+#define RT_PARK_DONE 0
+#define RT_PARK_BVH 1
+#define RT_PARK_KD 2
 template <bool COUNT, typename STACK>
-__device__ __forceinline__ bool trace_bvh_park(const RtDevScene &sc, const Vec3D o, const Vec3D d, int &hit, float &hbx,
-                                               float &hby, float &hbz, STACK &stk, Cnt &c, int cap, bool resume,
-                                               BvhPark &pk)
+__device__ __forceinline__ int trace_bvh_park(const RtDevScene &sc, const Vec3D o, const Vec3D d, int &hit, float &hbx,
+                                              float &hby, float &hbz, STACK &stk, Cnt &c, int cap, int resume,
+                                              bool defer_kd, BvhPark &pk)
 {
-    if (COUNT && !resume) c.v[RT_CNT_RAY]++;
+    if (COUNT && resume == RT_PARK_DONE) c.v[RT_CNT_RAY]++;
     hit = -1;
     float entry, exit_;
-    if (!bbox_hit(sc, o, d, entry, exit_)) return true;
+    if (!bbox_hit(sc, o, d, entry, exit_)) return RT_PARK_DONE;
     const float root_exit = exit_;
     float s_min = -INFINITY; // (the plain KD traversal)
     int tstar = -1;
     if (rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
-        if (!bvh4_query<COUNT, true>(sc, o, d, exit_, stk, c, cap, resume, pk)) return false;
+        if (resume != RT_PARK_KD) {
+            if (!bvh4_query<COUNT, true>(sc, o, d, exit_, stk, c, cap, resume == RT_PARK_BVH, pk)) return RT_PARK_BVH;
+            if (!(pk.best < root_exit)) return RT_PARK_DONE;
+            if (kd_certified<COUNT>(sc, o, d, entry, root_exit, pk.best, pk.tk, hit, hbx, hby, hbz, c))
+                return RT_PARK_DONE;
+            if (RT_KD_CERT && defer_kd) return RT_PARK_KD;
+        }
         s_min = pk.best;
-        if (!(s_min < root_exit)) return true;
         if (pk.tk >= 0) tstar = (int)sc.bvh_bary[pk.tk].tri;
     }
     hit = kd_bounded<COUNT>(sc, o, d, entry, root_exit, s_min, tstar, hbx, hby, hbz, stk, c);
-    return true;
+    if (COUNT && hit >= 0) c.cert[1]++;
+    return RT_PARK_DONE;
 }
 
 // ---- the occlusion query (rt_occluded, query.hip) ----

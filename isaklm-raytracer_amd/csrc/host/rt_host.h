@@ -81,7 +81,28 @@ struct PreparedHost {
     // bounds it); and the split values per axis as open-addressing hash sets
     int kd_grid = 0;
     float kd_grid_scale[3] = {0, 0, 0};
+    // the T* certificate's tables (bvh_common.h rt_kd_cert; scene_prepare.cpp build_kd_cert): per BVH
+    // leaf slot its safe box {lo.xyz, 0}, {hi.xyz, 0} (empty: lo = +inf, hi = -inf), and per axis the
+    // split values as an open-addressing hash set (4-slot buckets, load <= 0.25); kd_safe empty: no certificate
+    std::vector<RtF4> kd_safe;
+    std::vector<uint32_t> split_hash;
+    int split_hoff[3] = {0, 0, 0}, split_hshift[3] = {31, 31, 31};
+    RtKdCert kd_cert() const // (over these host arrays, for rt_kd_cert on the host)
+    {
+        RtKdCert kc;
+        kc.safe = kd_safe.empty() ? nullptr : kd_safe.data();
+        kc.hash = split_hash.data();
+        for (int a = 0; a < 3; ++a) {
+            kc.hoff[a] = split_hoff[a];
+            kc.hshift[a] = split_hshift[a];
+        }
+        kc.scale = bvh_scale;
+        return kc;
+    }
 };
+// fills kd_safe / split_hash (after the BVH and split_vals); RT_E_INVALID when the final pass finds a KD leaf
+// that meets a safe box without listing its triangle (an internal error: never on a consistent build)
+int build_kd_cert(PreparedHost &out, const Triangle *tris, const std::vector<uint32_t> &order);
 // fills the origin-cell tables from the prepared KD nodes (scene_prepare.cpp)
 void build_kd_starts(PreparedHost &out, const Bounding_Box &bounds);
 int prepare_host(const Triangle *tris, int ntris, const KD_Tree_Node *nodes, int nnodes, const int *indices,

@@ -129,6 +129,133 @@ void build_kd_starts(PreparedHost &out, const Bounding_Box &bounds)
     for (int a = 0; a < 3; ++a) out.kd_grid_scale[a] = (float)G / ext[a];
 }
 
+// The T* certificate's tables (bvh_common.h rt_kd_cert, DESIGN.md §5 "The certificate").
+//
+// Safe box of BVH slot k (triangle T): a box such that every KD leaf whose cell — the closed region
+// its ancestors' splits cut out of all space — meets it lists T.  It starts as T's vertex box grown by
+// tri_margin; one sweep over the leaves meeting it clips it, for each that does not list T, on the
+// axis where that leaf's cell is farthest from T's vertex box (create_kd_tree's rule, min <= split
+// left / max >= split right, guarantees one: a leaf without T lies beyond a split T is strictly on
+// the other side of; a tree without it empties the box, and the slot never certifies).  Clipping only
+// shrinks the box, so leaves passed before still list T or still miss it.  A second sweep re-checks
+// the final box and fails the preparation on any leaf without T: the guarantee rests on that sweep,
+// not on the builder's rule.
+namespace {
+struct CertCell {
+    uint32_t node;
+    float lo[3], hi[3];
+};
+// the leaves whose cell meets box [blo, bhi] and that do not list triangle t: clip = true shrinks the box
+// away from each (tlo / thi: T's vertex box), clip = false returns false at the first
+bool cert_sweep(const PreparedHost &h, uint32_t t, float *blo, float *bhi, const float *tlo, const float *thi, bool clip)
+{
+    CertCell stk[2 * RT_STACK_DEPTH + 2];
+    int sp = 0;
+    stk[sp++] = CertCell{0u, {-INFINITY, -INFINITY, -INFINITY}, {INFINITY, INFINITY, INFINITY}};
+    while (sp > 0) {
+        const CertCell c = stk[--sp];
+        bool meets = true;
+        for (int a = 0; a < 3; ++a) meets = meets && std::max(c.lo[a], blo[a]) <= std::min(c.hi[a], bhi[a]);
+        if (!meets) continue;
+        const uint32_t x = h.nodes[2 * (size_t)c.node], y = h.nodes[2 * (size_t)c.node + 1];
+        if ((y & 3u) != RT_LEAF_TAG) {
+            const int a = (int)(y & 3u);
+            const float split = bitsf(x);
+            CertCell l = c, r = c;
+            l.node = c.node + 1;
+            l.hi[a] = std::min(l.hi[a], split);
+            r.node = y >> 2;
+            r.lo[a] = std::max(r.lo[a], split);
+            stk[sp++] = r;
+            stk[sp++] = l;
+            continue;
+        }
+        bool listed = false;
+        for (uint32_t e = x, e1 = x + (y >> 2); e < e1 && !listed; ++e) listed = h.isect_tri[e] == t;
+        if (listed) continue;
+        if (!clip) return false;
+        int best = -1;
+        float gap = 0.0f;
+        bool below = false;
+        for (int a = 0; a < 3; ++a) {
+            if (c.hi[a] < tlo[a] && (best < 0 || tlo[a] - c.hi[a] > gap)) {
+                best = a, gap = tlo[a] - c.hi[a], below = true;
+            }
+            if (c.lo[a] > thi[a] && (best < 0 || c.lo[a] - thi[a] > gap)) {
+                best = a, gap = c.lo[a] - thi[a], below = false;
+            }
+        }
+        if (best < 0) { // no axis separates the cell from T (not create_kd_tree's tree): never certify
+            for (int a = 0; a < 3; ++a) blo[a] = INFINITY, bhi[a] = -INFINITY;
+            return true;
+        }
+        if (below) blo[best] = std::nextafterf(c.hi[best], INFINITY);
+        else bhi[best] = std::nextafterf(c.lo[best], -INFINITY);
+    }
+    return true;
+}
+} // namespace
+
+int build_kd_cert(PreparedHost &out, const Triangle *tris, const std::vector<uint32_t> &order)
+{
+    // the split values per axis as open-addressing sets: keys = the bits of v + 0 (-0 is +0)
+    out.split_hash.clear();
+    for (int a = 0; a < 3; ++a) {
+        const size_t n = (size_t)(out.split_off[a + 1] - out.split_off[a]);
+        int bits = 2; // (whole 4-slot buckets; load <= 0.25: a lookup rarely reads a second bucket)
+        while (((size_t)1 << bits) < 4 * n) ++bits;
+        const uint32_t shift = 32u - (uint32_t)bits, mask = (1u << bits) - 1u;
+        out.split_hoff[a] = (int)out.split_hash.size();
+        out.split_hshift[a] = (int)shift;
+        out.split_hash.resize(out.split_hash.size() + ((size_t)1 << bits), RT_SPLIT_EMPTY);
+        uint32_t *tab = out.split_hash.data() + out.split_hoff[a];
+        for (size_t k = 0; k < n; ++k) {
+            const uint32_t key = fbits(out.split_vals[(size_t)out.split_off[a] + k] + 0.0f);
+            uint32_t i = ((key * 0x9E3779B1u) >> shift) & ~3u; // from its home bucket's start (rt_split_member)
+            while (tab[i] != RT_SPLIT_EMPTY && tab[i] != key) i = (i + 1) & mask;
+            tab[i] = key;
+        }
+    }
+    const size_t ns = order.size();
+    out.kd_safe.assign(2 * ns, f4(0, 0, 0, 0));
+    long long bad = 0;
+#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : bad)
+    for (long long k = 0; k < (long long)ns; ++k) {
+        const Triangle &t = tris[order[(size_t)k]];
+        const float *p1 = &t.p1.x, *p2 = &t.p2.x, *p3 = &t.p3.x;
+        const RtIsectBary &r = out.bvh_bary[(size_t)k];
+        const RtF4 &pl = out.bvh_a[(size_t)k];
+        const float m = tri_margin(rt_v3(r.b.x, r.b.y, r.b.z), rt_v3(r.c.x, r.c.y, r.c.z), rt_v3(r.d.x, r.d.y, r.d.z),
+                                   bitsf(r.rd), pl.x, pl.y, pl.z);
+        float tlo[3], thi[3], blo[3], bhi[3];
+        bool usable = std::isfinite(m);
+        for (int a = 0; a < 3; ++a) {
+            tlo[a] = fminf(p1[a], fminf(p2[a], p3[a]));
+            thi[a] = fmaxf(p1[a], fmaxf(p2[a], p3[a]));
+            usable = usable && std::isfinite(p1[a]) && std::isfinite(p2[a]) && std::isfinite(p3[a]);
+            blo[a] = tlo[a] - m;
+            bhi[a] = thi[a] + m;
+        }
+        if (usable) {
+            (void)cert_sweep(out, r.tri, blo, bhi, tlo, thi, true);
+            usable = blo[0] <= bhi[0] && blo[1] <= bhi[1] && blo[2] <= bhi[2];
+        }
+        if (!usable) { // (an always-tested triangle's box is the whole scene: no safe box)
+            for (int a = 0; a < 3; ++a) blo[a] = INFINITY, bhi[a] = -INFINITY;
+        } else if (!cert_sweep(out, r.tri, blo, bhi, tlo, thi, false)) {
+            ++bad;
+        }
+        out.kd_safe[2 * (size_t)k] = f4(blo[0], blo[1], blo[2], 0.0f);
+        out.kd_safe[2 * (size_t)k + 1] = f4(bhi[0], bhi[1], bhi[2], 0.0f);
+    }
+    if (bad > 0) {
+        out.kd_safe.clear();
+        rt_set_error("prepare: %lld safe boxes meet a KD leaf that does not list their triangle", bad);
+        return RT_E_INVALID;
+    }
+    return RT_OK;
+}
+
 int prepare_host(const Triangle *tris, int ntris, const KD_Tree_Node *nodes, int nnodes, const int *indices,
                  int nindices, const int *lights, int nlights, Bounding_Box bounds, PreparedHost &out)
 {
@@ -337,6 +464,13 @@ int prepare_host(const Triangle *tris, int ntris, const KD_Tree_Node *nodes, int
         }
         out.split_off[3] = (int)out.split_vals.size();
         if (nan_split) out.bvh_depth = -1;
+    }
+    // the T* certificate's safe boxes and split sets (bvh_common.h rt_kd_cert)
+    out.kd_safe.clear();
+    out.split_hash.clear();
+    if (out.bvh_depth >= 0) {
+        const int crc = build_kd_cert(out, tris, bvh.order);
+        if (crc != RT_OK) return crc;
     }
 
     // --- lights: one padding entry for the xi == 1.0 draw -----

@@ -63,11 +63,15 @@
                               // dispatch); the finisher's lanes ran their deep paths themselves
 #define RT_DEV_WIDE_OVERFLOW 34 // wf_long bounces whose wide s_min query overflowed its frontier (traced by the wide
                                // KD traversal instead: identical results)
+// counting instantiations only (RT_TRAVERSAL_BOUNDED_COUNTED; rt_kd_cert_stats): hit rays of bounded rays the T*
+// certificate covered / that ran the KD descent
+#define RT_DEV_CERT_OK 35
+#define RT_DEV_CERT_FALLBACK 36
 #define RT_DEV_WORDS 48
 // rt_wavefront_join's return when its hand-off check found stranded pixels (-1: a HIP failure)
 #define RT_WAVEFRONT_INCOMPLETE (-2)
 static_assert(RT_DEV_HIST + RT_DEV_HIST_BINS <= RT_DEV_CHECKED && RT_DEV_MISRAY + 4 <= RT_DEV_OWED_PIXELS &&
-                  RT_DEV_WIDE_OVERFLOW < RT_DEV_WORDS,
+                  RT_DEV_CERT_FALLBACK < RT_DEV_WORDS,
               "deviation block");
 
 struct RtDevMaterial {          // 64 B
@@ -94,6 +98,15 @@ struct RtIsectBary {            // 64 B, one per leaf entry
     uint32_t pad[2];
 };
 static_assert(sizeof(RtIsectBary) == 64, "RtIsectBary");
+
+// The T* certificate's tables (bvh_common.h rt_kd_cert; host/scene_prepare.cpp build_kd_cert)
+struct RtKdCert {
+    const RtF4 *safe;           // 2 per BVH leaf slot: {lo.xyz, -}, {hi.xyz, -}: every KD leaf whose closed cell meets
+                                // the box lists the slot's triangle; lo > hi: empty (never certifies); nullptr: none
+    const uint32_t *hash;       // per axis an open-addressing set of the KD split values (RT_SPLIT_EMPTY: unused)
+    int hoff[3], hshift[3];     // axis a: hash[hoff[a] + i], i < 2^(32 - hshift[a])
+    float scale;                // bvh_scale (rt_cert_delta)
+};
 
 struct RtDevScene {
     const uint32_t *nodes;      // 2 words per node
@@ -125,6 +138,7 @@ struct RtDevScene {
     const uint32_t *kd_cell;    // per cell of a kd_grid^3 grid over the scene box: {start node, row offset << 5 | depth}
     int kd_grid;                // cell of p: ((p - bmin) * kd_gscale), clamped to [0, kd_grid - 1]
     float kd_gscale[3];
+    RtKdCert kd_cert;           // kd_cert.safe == nullptr: no certificate (every ray runs the KD descent)
 };
 
 // BVH child reference: an inner node's index, or RT_BVH_LEAF | first << 3 |

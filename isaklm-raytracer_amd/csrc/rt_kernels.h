@@ -17,9 +17,11 @@ enum { PRIMARY = 0, DIFFUSE = 1, SPECULAR = 2, METALLIC = 3, TRANSMISSION = 4 };
 
 struct Cnt {
     unsigned long long v[RT_CNT_COUNT]; // RT_CNT_* ; v[RT_CNT_MAXDEPTH] is a max
+    unsigned long long cert[2];         // hit rays of bounded rays: certified, fallen back (bvh_trace.h kd_certified)
     __device__ void zero()
     {
         for (int k = 0; k < RT_CNT_COUNT; ++k) v[k] = 0;
+        cert[0] = cert[1] = 0;
     }
     __device__ void path_end(int depth)
     {
@@ -568,6 +570,16 @@ __device__ __forceinline__ void flush_counters(Cnt &c, unsigned long long *out)
         for (int k = 0; k < RT_CNT_COUNT; ++k)
             if (k != RT_CNT_MAXDEPTH && c.v[k]) atomicAdd(out + k, c.v[k]);
         atomicMax(out + RT_CNT_MAXDEPTH, c.v[RT_CNT_MAXDEPTH]);
+    }
+}
+
+// the certificate's two counters (counting instantiations), into the deviation block (RT_DEV_CERT_*)
+__device__ __forceinline__ void flush_cert_counters(Cnt &c, unsigned long long *dev_stats)
+{
+    for (int k = 0; k < 2; ++k) {
+        unsigned long long v = c.cert[k];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(dev_stats + RT_DEV_CERT_OK + k, v);
     }
 }
 

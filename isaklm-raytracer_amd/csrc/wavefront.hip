@@ -124,6 +124,12 @@ static_assert(WF_BLOCK % WF_TBLOCK == 0 && WF_TBLOCK % 64 == 0, "WF_TBLOCK must 
                       // after round 6's VALU cuts: 4 / 5 / 6 / 7 / 8 / 12 / 16 = 723-727 / 733 / 738-742 / 739-741 /
                       // 712-731 / 715 / 699-700 Msamples/s, profiles/r06/ab/ ab16-ab17)
 #endif
+#ifndef WF_KD_PEND_MIN
+#define WF_KD_PEND_MIN 8 // wf_finish_bvh: lanes of a wave waiting for their KD descent (rays the T* certificate does
+                         // not cover, RT_PARK_KD) before a loop trip runs them; fewer wait — unless the wave has
+                         // nothing else to do (1 / 4 / 8 / 16 / 64 = 770-777 / 782-785 / 763-772 / 753-754 / 319-321
+                         // Msamples/s, profiles/kd_cert/pend_min_sweep.txt)
+#endif
 #ifndef WF_FIN_BVH_WAVES
 #define WF_FIN_BVH_WAVES 4 // wf_finish_bvh occupancy target: 4 waves/SIMD (128 VGPRs, 29 spilled) run the bench at
                            // 5's rate (566.8-572.2 vs 562.8-573.1 Msamples/s, round 6) with a third of its HBM traffic
@@ -1450,7 +1456,11 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
     __shared__ int s_pk_sp[WF_BLOCK];
     __shared__ float s_pk_best[WF_BLOCK];
     __shared__ int s_pk_tk[WF_BLOCK];
-    bool parked = false;
+    // RT_PARK_KD: the lane's ray is past its query and not covered by the T* certificate — only the KD
+    // descent is left (s_min and its slot in s_pk_best / s_pk_tk).  One such lane must not make its wave
+    // walk a descent alone: the pending descents run together, in a trip where WF_KD_PEND_MIN lanes wait
+    // for theirs or no lane of the wave has anything else to do.
+    int parked = RT_PARK_DONE;
 #endif
     while (true) {
         // (fresh) pixels whose passes are done are let go — unless a later chained call queued
@@ -1691,15 +1701,22 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
         quiet_trips = 0;
         idle_trips = 0;
         bool to_long = false;
+#if WF_BVH_PARK && RT_KD_CERT
+        const unsigned long long kd_pend = __ballot(active && parked == RT_PARK_KD);
+        const bool run_kd = kd_pend != 0ull && (__popcll(kd_pend) >= WF_KD_PEND_MIN ||
+                                                __ballot(active && parked != RT_PARK_KD) == 0ull);
+        if (active && (parked != RT_PARK_KD || run_kd)) {
+#else
         if (active) {
+#endif
             float bx = 0.0f, by = 0.0f, bz = 0.0f;
 #if WF_BVH_PARK
             int hit;
             BvhPark pk{0u, 0, 0.0f, -1};
-            if (parked) pk = BvhPark{s_pk_cur[tid], s_pk_sp[tid], s_pk_best[tid], s_pk_tk[tid]};
-            const bool done = trace_bvh_park<COUNT>(sc, p.ro, p.rd, hit, bx, by, bz, stk, c, WF_BVH_PARK, parked, pk);
-            parked = !done;
-            if (parked) {
+            if (parked != RT_PARK_DONE) pk = BvhPark{s_pk_cur[tid], s_pk_sp[tid], s_pk_best[tid], s_pk_tk[tid]};
+            parked = trace_bvh_park<COUNT>(sc, p.ro, p.rd, hit, bx, by, bz, stk, c, WF_BVH_PARK, parked, true, pk);
+            const bool done = parked == RT_PARK_DONE;
+            if (!done) {
                 s_pk_cur[tid] = pk.cur;
                 s_pk_sp[tid] = pk.sp;
                 s_pk_best[tid] = pk.best;
@@ -1747,7 +1764,10 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
             }
         }
     }
-    if (COUNT) flush_counters(c, fr.counters);
+    if (COUNT) {
+        flush_counters(c, fr.counters);
+        flush_cert_counters(c, fr.dev_stats);
+    }
     if (st.span && lane == 0) atomicMax(st.span + 1, __builtin_amdgcn_s_memrealtime());
     if (st.fin_live) { // this wave's hand-offs are published: the persistent wf_long may stop once all are past here
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2176,11 +2196,17 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
                 // is abandoned and counted, and the ray takes the wide KD traversal below, as do rays
                 // the bound does not apply to (rt_bounded_ray)
                 bool traced = false;
+                bool certified = false;
                 if (st.long_wide && rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
                     float s_min = ex;
                     int tk = -1;
                     traced = wide_smin<COUNT>(sc, o, d, ex, wsm_lds(W.F, W.key, st.long_wide == 2), s_min, tk, c);
-                    if (traced && s_min < ex) { // (every lane: kd_bounded_wave)
+                    // the T* certificate (bvh_trace.h kd_certified) on the wave's one ray, every lane alike: where
+                    // it holds the bounce needs no descent
+                    if (traced && s_min < ex)
+                        certified = kd_certified<COUNT>(sc, o, d, en, ex, s_min, tk, hit, bx, by, bz, c, lane == 0);
+                    if (traced && s_min < ex && !certified) {
+                        // (every lane: kd_bounded_wave)
                         LdsStack1 ks{reinterpret_cast<uint2 *>(W.mark)}; // (128 ints: WSM_KD_STACK entries)
                         const int tstar = tk >= 0 ? (int)sc.bvh_bary[tk].tri : -1;
                         hit = kd_bounded_wave<COUNT>(sc, o, d, en, ex, s_min, tstar, bx, by, bz, ks,
@@ -2194,6 +2220,7 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
                     if (nf > 0) wide_trace_from<COUNT>(sc, o, d, nf, W, lane == 0, hit, bx, by, bz, c);
                     else wide_trace<COUNT>(sc, o, d, en, ex, W, lane == 0, hit, bx, by, bz, c);
                 }
+                if (COUNT && lane == 0 && hit >= 0 && !certified) c.cert[1]++; // (found by a KD descent)
             }
             want = 0;
             if (lane == 0) {
@@ -2287,7 +2314,10 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
         t_idle = __builtin_amdgcn_s_memrealtime();
         n_idle = 0;
     }
-    if (COUNT) flush_counters(c, fr.counters);
+    if (COUNT) {
+        flush_counters(c, fr.counters);
+        flush_cert_counters(c, fr.dev_stats);
+    }
 }
 
 // ---------------------------------------------------------------- launcher
@@ -2738,7 +2768,13 @@ int launch_whole_now(Workspace &w, int dev, const RtDevScene &sc, const RtDevFra
     // / the sampling interval, so a small frame does not hold the 2 x 4M-record maximum
     const int par = (int)(w.call_seq & 1);
     if (check_mask != 0xFFFFFFFFu) {
-        const unsigned long long want = (unsigned long long)slots * (unsigned long long)fr.passes * 8ull /
+        // (every ray recorded — check_interval 1, the tests' setting — leaves that average no slack: sized for the
+        // most a sample can trace before its hand-off, an extension and a shadow ray per bounce, up to
+        // WF_CHECK_CAP — a frame beyond WF_CHECK_CAP / (2 * depth + 2) samples per call can still drop records,
+        // which check_dropped reports)
+        const unsigned long long per_sample =
+            check_mask == 0u ? 2ull * (unsigned long long)(long_depth > 0 ? long_depth : RT_DEEP_PATH) + 2ull : 8ull;
+        const unsigned long long want = (unsigned long long)slots * (unsigned long long)fr.passes * per_sample /
                                         ((unsigned long long)check_mask + 1ull);
         uint32_t cap = 1u << 16;
         while (cap < want && cap < WF_CHECK_CAP) cap <<= 1;

@@ -148,6 +148,16 @@ def deviation_stats(reset=False):
     return out
 
 
+def kd_cert_stats(reset=False):
+    """rt_kd_cert_stats: (certified, fallback) hit rays of the bounded traversal
+    in counting renders (TRAVERSAL_BOUNDED_COUNTED) since the last reset."""
+    if not hasattr(lib(), "rt_kd_cert_stats"):
+        raise RtError(f"{LIB_PATH} was built before rt_kd_cert_stats was added (within ABI {ABI_VERSION}): rebuild it")
+    a, b = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+    check(lib().rt_kd_cert_stats(ctypes.byref(a), ctypes.byref(b), int(reset)))
+    return int(a.value), int(b.value)
+
+
 def join(stream=None):
     """rt_join: `stream` (None: the host) waits for every render's device work,
     chained calls' deep-path tails included."""
@@ -224,6 +234,8 @@ def lib():
         L.rt_tonemap.argtypes = [G_Buffer, vp, i, i, vp]
         L.rt_save_render.argtypes = [G_Buffer, i, i, ctypes.c_char_p]
         L.rt_deviation_stats.argtypes = [ctypes.POINTER(RtDeviations), i]
+        if hasattr(L, "rt_kd_cert_stats"):  # (added within ABI 12: an earlier ABI-12 library lacks it)
+            L.rt_kd_cert_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong), i]
         L.rt_join.argtypes = [vp]
         L.rt_profile_history.argtypes = [ctypes.POINTER(RtProfile), i, ctypes.POINTER(i), i]
         L.rt_default_query_options.argtypes = [ctypes.POINTER(RtQueryOptions)]
