@@ -30,6 +30,7 @@
 
 #include "bvh_trace.h"
 #include "rt_kernels.h"
+#include "wf_check_grid.h"
 
 using namespace rtk;
 
@@ -117,7 +118,9 @@ static_assert(WF_BLOCK % WF_TBLOCK == 0 && WF_TBLOCK % 64 == 0, "WF_TBLOCK must 
 #define WF_BVH_WAVES 6  // wf_trace_bvh occupancy target
 #endif
 #ifndef WF_CHECK_BLOCKS
-#define WF_CHECK_BLOCKS 256 // wf_check's grid (it runs beside the next call's finisher)
+#define WF_CHECK_BLOCKS 256 // wf_check's grid for a chained call (it runs beside the next call's finisher or the
+                            // drain), and the least an unchained call gets: alone on the chip, that one's grid
+                            // follows its records up to the spill area's lanes (wf_check_grid.h)
 #endif
 #ifndef WF_BVH_PARK
 #define WF_BVH_PARK 6 // wf_finish_bvh: BVH node steps per loop trip before a lane's query parks (0: never; re-swept
@@ -125,10 +128,11 @@ static_assert(WF_BLOCK % WF_TBLOCK == 0 && WF_TBLOCK % 64 == 0, "WF_TBLOCK must 
                       // 712-731 / 715 / 699-700 Msamples/s, profiles/r06/ab/ ab16-ab17)
 #endif
 #ifndef WF_KD_PEND_MIN
-#define WF_KD_PEND_MIN 8 // wf_finish_bvh: lanes of a wave waiting for their KD descent (rays the T* certificate does
+#define WF_KD_PEND_MIN 4 // wf_finish_bvh: lanes of a wave waiting for their KD descent (rays the T* certificate does
                          // not cover, RT_PARK_KD) before a loop trip runs them; fewer wait — unless the wave has
                          // nothing else to do (1 / 4 / 8 / 16 / 64 = 770-777 / 782-785 / 763-772 / 753-754 / 319-321
-                         // Msamples/s, profiles/kd_cert/pend_min_sweep.txt)
+                         // Msamples/s, profiles/kd_cert/pend_min_sweep.txt; 8 shipped with the certificate, 4 since
+                         // the GPU suite ran on it: profiles/guard_refit/)
 #endif
 #ifndef WF_FIN_BVH_WAVES
 #define WF_FIN_BVH_WAVES 4 // wf_finish_bvh occupancy target: 4 waves/SIMD (128 VGPRs, 29 spilled) run the bench at
@@ -2736,6 +2740,7 @@ int launch_whole_now(Workspace &w, int dev, const RtDevScene &sc, const RtDevFra
     const size_t slots = (size_t)fr.width * fr.height;
     // a resetting call (sample_count 0) neither continues nor opens a chain: its reset of a pixel
     // must come before any later pass, and a chained lane may reach a pixel before it does
+    const bool chain_asked = overlap; // (a chain's first, resetting call included: the next call's finisher follows it)
     overlap = overlap && !fr.reset;
     // every wave slot at the finisher's occupancy (MI355X: 256 CUs x 4 SIMDs x 4 waves / 4 waves per
     // block = 1,024 blocks), the last WF_LONG_BLOCKS of them left to wf_long
@@ -2767,6 +2772,7 @@ int launch_whole_now(Workspace &w, int dev, const RtDevScene &sc, const RtDevFra
     // sized from the call's rays: <= 8 rays per sample (deep paths go to wf_long; owed passes are few)
     // / the sampling interval, so a small frame does not hold the 2 x 4M-record maximum
     const int par = (int)(w.call_seq & 1);
+    unsigned long long chk_want = 0; // the most records the call is sized for (wf_check's grid follows it)
     if (check_mask != 0xFFFFFFFFu) {
         // (every ray recorded — check_interval 1, the tests' setting — leaves that average no slack: sized for the
         // most a sample can trace before its hand-off, an extension and a shadow ray per bounce, up to
@@ -2776,6 +2782,7 @@ int launch_whole_now(Workspace &w, int dev, const RtDevScene &sc, const RtDevFra
             check_mask == 0u ? 2ull * (unsigned long long)(long_depth > 0 ? long_depth : RT_DEEP_PATH) + 2ull : 8ull;
         const unsigned long long want = (unsigned long long)slots * (unsigned long long)fr.passes * per_sample /
                                         ((unsigned long long)check_mask + 1ull);
+        chk_want = want;
         uint32_t cap = 1u << 16;
         while (cap < want && cap < WF_CHECK_CAP) cap <<= 1;
         if (cap > w.chk_cap) { // (grown: after every wf_check that reads the old records)
@@ -2892,7 +2899,16 @@ int launch_whole_now(Workspace &w, int dev, const RtDevScene &sc, const RtDevFra
         cs.spill = cp.st.spill;
         if (!cs.spill) return -1;
         if (hipStreamWaitEvent(cp.stream, pp.fin_done, 0) != hipSuccess) return -1;
-        hipLaunchKernelGGL(wf_check, dim3(WF_CHECK_BLOCKS), dim3(WF_BLOCK), 0, cp.stream, sc, cs, fr.dev_stats);
+        // Its grid: WF_CHECK_BLOCKS beside a chain's next finisher; a call that overlaps nothing runs the check
+        // alone on the chip, inside the caller's wait, and gets a lane per record it may hold.  At most
+        // spill_threads / WF_BLOCK blocks either way: a lane's KD stack spills to cs.spill[gtid + k * spill_threads],
+        // so a lane at or past spill_threads would write into its neighbours' entries and past the area's end
+        const int cgrid = wf_check_grid(chain_asked, chk_want, cs.chk_cap, cs.spill_threads, WF_BLOCK, WF_CHECK_BLOCKS);
+        if (cgrid < 1 || (size_t)cgrid * WF_BLOCK > (size_t)cs.spill_threads) {
+            fprintf(stderr, "[wf] wf_check grid %d blocks exceeds the spill area's %d lanes\n", cgrid, cs.spill_threads);
+            return -1;
+        }
+        hipLaunchKernelGGL(wf_check, dim3(cgrid), dim3(WF_BLOCK), 0, cp.stream, sc, cs, fr.dev_stats);
         if (hipGetLastError() != hipSuccess) return -1;
         if (hipEventRecord(w.chk_done[par], cp.stream) != hipSuccess || hipEventRecord(cp.join, cp.stream) != hipSuccess)
             return -1;
