@@ -68,7 +68,9 @@ extern "C" {
  * an addition only.  The radiance query (rt_trace_paths, RtPathOptions,
  * rt_default_path_options) was added within version 12 — new symbols and a
  * new struct, nothing existing moved; RT_HAS_TRACE_PATHS is its compile-time
- * feature test.
+ * feature test.  Temporal reprojection (rt_reproject, rt_reproject_host,
+ * rt_default_reproject_options, RtReprojectOptions) was added within version
+ * 12 in the same way; RT_HAS_REPROJECT is its feature test.
  * An integrator checks
  * rt_abi_version() == RT_ABI_VERSION at start-up: a binary built against an
  * older header would otherwise link (C linkage) and mis-pass arguments. */
@@ -813,6 +815,81 @@ int rt_denoise_host(const float *fb, const float *sq, const int *count, const fl
 /* rt_tonemap's colour math (correct_color -> RGBA8) for a float RGB mean-radiance buffer (width*height x 3
  * floats, e.g. rt_denoise's output) */
 int rt_tonemap_rgb(const float *rgb_device, uint8_t *rgba_device, int width, int height, void *stream);
+
+/* ---------------- temporal reprojection (ABI 12, an addition) ----------------
+ * Carries a frame's samples over to a moved camera, where the reference's
+ * main() calls reset_frame (rt/main.cu:114-155) and starts again at 0 spp.
+ * The history needs no new type: a reprojected frame is another G_Buffer —
+ * per-pixel sums frame_buffer and squared_luminance and a per-pixel
+ * sample_count — which rt_render with sample_count != 0 adds passes to,
+ * rt_denoise takes its variance from and rt_tonemap divides:
+ *
+ *     rt_render_aov(scene, cam_new, W, H, &aov_new, NULL);
+ *     rt_reproject(g_old, &aov_old, cam_old, &aov_new, cam_new, W, H, g_new, NULL);   instead of a reset
+ *     rt_render(scene, g_new, cam_new, 1, &opt);                                      adds passes to the carried sums
+ *
+ * For every pixel of the new frame that hit something, its first hit (the
+ * pixel-centre ray times dst_aov->depth, kept relative to the old camera) is
+ * projected into the old frame.  A projection within 1/64 pixel of a pixel
+ * centre takes that pixel alone, any other the four bilinear taps around it.
+ * A tap counts if it lies in the frame, has samples, hit something, and shows
+ * the same surface: its depth within depth_tol (relative) of the point's
+ * distance from the old camera, its normal within normal_min (a cosine) of
+ * the new pixel's and, with match_triangle, the same triangle.  If the
+ * counting taps hold at least 1/16 of the weight, the pixel gets their
+ * weighted mean radiance and mean squared luminance times n, with
+ * n = min(the counting taps' sample counts, max_history) as its sample_count;
+ * a lone tap that keeps its whole count is copied bit for bit (an unmoved
+ * camera returns the frame itself).  Every other pixel — a miss, a point
+ * behind or outside the old frame, a disocclusion, a carried sum that is NaN
+ * or infinite (it would spread with every later move) — is reset: sums 0, count 0,
+ * which rt_render's adaptive test and rt_denoise take as "no samples yet".
+ * DESIGN.md "Temporal reprojection" defines every operation: all are correctly
+ * rounded float32 operations in a fixed order, and rt_reproject (GPU) and
+ * rt_reproject_host (CPU) give the same bits.
+ *
+ * Writes dst.frame_buffer, dst.squared_luminance and dst.sample_count for all
+ * width*height pixels and nothing else.  random_numbers is neither read nor
+ * written in either G_Buffer: put the same RNG array in both and the per-pixel
+ * streams simply continue.  dst's three written arrays must not overlap src's
+ * three (the call is a gather).  AOVs: depth and normal are required on both
+ * sides, triangle is optional on both, albedo is unused.
+ *
+ * rt_reproject reads a frame: like rt_tonemap and rt_denoise it first joins
+ * the renders (chained calls' deep-path tails included) on `stream`.  It keeps
+ * no per-device workspace, so calls are ordered by their streams alone.  A
+ * following rt_render on dst is ordered behind it by the stream (or by the
+ * NULL-stream call having been synchronous).
+ * NaN and infinite depths, positions and angles are safe: they fail the
+ * projection's compares and the pixel (for a camera whose yaw, pitch or FOV is
+ * NaN, infinite or beyond +-2^19: every pixel) is reset.
+ * Errors before any GPU call (RT_E_INVALID): a null required pointer, a bad
+ * size (width or height < 1, width * height > 2^31 - 1; a 1-pixel-wide frame
+ * has no camera — its half width is 0 — and resets every pixel), overlapping
+ * src and dst arrays, max_history or match_triangle out of range, a negative,
+ * NaN or infinite depth_tol, normal_min outside (-1, 1]. */
+#define RT_HAS_REPROJECT 1
+typedef struct RtReprojectOptions {
+    int   max_history;    /* cap of the carried per-pixel sample count; 0 = default (64); 1 .. 1<<20 */
+    float depth_tol;      /* 0 = default (0.02): a source tap is the same surface if |z_src - z_expected| <= depth_tol * z_expected */
+    float normal_min;     /* 0 = default (0.95): ... and dot(n_new, n_src) >= normal_min;  (-1, 1] */
+    int   match_triangle; /* 0 = default on (1) when both triangle buffers are given: ... and the triangle ids are equal; -1 = off */
+    void *stream;         /* hipStream_t; NULL = synchronous */
+    unsigned long long *stats_device; /* optional, 3 u64, adds: [0] pixels, [1] pixels that kept history (count_out > 0),
+                                         [2] samples carried (sum of count_out) */
+} RtReprojectOptions;
+void rt_default_reproject_options(RtReprojectOptions *opt);
+/* opt NULL = the defaults */
+int rt_reproject(G_Buffer src, const RtAovBuffers *src_aov, Camera src_camera,
+                 const RtAovBuffers *dst_aov, Camera dst_camera, int width, int height,
+                 G_Buffer dst, const RtReprojectOptions *opt);
+/* the same arithmetic on host arrays, same layouts (fb: 3 floats per pixel); the triangle arrays and stats may
+ * be NULL; stats is written (not added to); opt->stream and opt->stats_device are ignored */
+int rt_reproject_host(const float *src_fb, const float *src_sq, const int *src_count,
+                      const float *src_depth, const float *src_normal, const int32_t *src_triangle, Camera src_camera,
+                      const float *dst_depth, const float *dst_normal, const int32_t *dst_triangle, Camera dst_camera,
+                      int width, int height, float *dst_fb, float *dst_sq, int *dst_count,
+                      unsigned long long stats[3], const RtReprojectOptions *opt);
 
 /* ---------------- multi-GPU shards ----------------
  * One process per GPU.  Rank 0 makes an id (rt_comm_unique_id), ships its

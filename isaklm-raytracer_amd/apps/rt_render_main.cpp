@@ -13,6 +13,12 @@
 //                  [--tolerance T] [--max-depth D] [--kernel mega|wavefront]
 //                  [--shard G N] [--device D] [--out PNG] [--quiet]
 //                  [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]
+//                  [--reproject-to "PX PY PZ YAW PITCH" [--spp2 N]]
+// --reproject-to moves the camera after the --spp samples (FOV and aperture
+// stay): instead of the reference's reset the frame is carried over to the new
+// camera (rt_reproject, guided by rt_render_aov of both cameras) into a second
+// G_Buffer that shares the first one's RNG array, --spp2 more samples are
+// rendered on top, and --out (and --denoise's image) show that second frame.
 // --aov writes the first-hit feature buffers of the pixel-centre rays
 // (rt_render_aov) before the render loop: PREFIX.albedo.pfm and
 // PREFIX.normal.pfm (PF, 3 floats per pixel) and PREFIX.depth.pfm (Pf; inf =
@@ -49,7 +55,8 @@ void usage()
             "usage: rt_render [--scene FILE | --generate NAME DIR] [--width W] [--height H] [--spp N]\n"
             "                 [--passes P] [--adaptive 0|1] [--min-samples N] [--tolerance T] [--max-depth D]\n"
             "                 [--kernel mega|wavefront] [--shard G N] [--device D] [--out PNG] [--quiet]\n"
-            "                 [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]\n");
+            "                 [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]\n"
+            "                 [--reproject-to \"PX PY PZ YAW PITCH\" [--spp2 N]]\n");
 }
 
 // PFM: "PF" (3 channels) or "Pf" (1), width height, a negative scale = little-endian, rows bottom to top
@@ -79,7 +86,16 @@ void free_aovs(RtAovBuffers *b)
     if (b->depth) rt_free(b->depth);
     if (b->normal) rt_free(b->normal);
     if (b->albedo) rt_free(b->albedo);
+    if (b->triangle) rt_free(b->triangle);
     b->depth = b->normal = b->albedo = nullptr;
+    b->triangle = nullptr;
+}
+
+// render_aovs plus the triangle ids: rt_reproject's guides
+int render_guides(rt_scene_t scene, Camera camera, int width, int height, RtAovBuffers *b)
+{
+    if (rt_device_alloc((void **)&b->triangle, (size_t)width * height * 4) != RT_OK) return fail("aov buffers");
+    return render_aovs(scene, camera, width, height, b);
 }
 
 // --aov: the buffers downloaded and written as PFM files
@@ -133,8 +149,9 @@ int write_denoised(G_Buffer g_buffer, const RtAovBuffers &b, int width, int heig
 
 int main(int argc, char **argv)
 {
-    std::string scene_path, gen_name, gen_dir, out = "render.png", checkpoint, resume, aov;
+    std::string scene_path, gen_name, gen_dir, out = "render.png", checkpoint, resume, aov, reproject_to;
     int width = 1920, height = 1080, spp = 5000, passes = 64, adaptive = 1, min_samples = 100, max_depth = 0;
+    int spp2 = 0;
     int device = 0, shard_id = 0, num_shards = 1, kernel = RT_KERNEL_WAVEFRONT;
     float tolerance = 0.05f;
     bool quiet = false, denoise = false;
@@ -166,12 +183,15 @@ int main(int argc, char **argv)
         else if (a == "--resume") resume = next();
         else if (a == "--aov") aov = next();
         else if (a == "--denoise") denoise = true;
+        else if (a == "--reproject-to") reproject_to = next();
+        else if (a == "--spp2") spp2 = atoi(next());
         else {
             usage();
             return 2;
         }
     }
-    if (scene_path.empty() == gen_name.empty() || width <= 0 || height <= 0 || spp <= 0 || passes <= 0) {
+    if (scene_path.empty() == gen_name.empty() || width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || spp2 < 0 ||
+        (spp2 > 0 && reproject_to.empty())) {
         usage();
         return 2;
     }
@@ -235,15 +255,53 @@ int main(int argc, char **argv)
     }
     if (rt_synchronize() != RT_OK) return fail("synchronize");
     const double render_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-    if (rt_save_render(g_buffer, width, height, out.c_str()) != RT_OK) return fail("save_render");
+
+    // --reproject-to: the camera moves; where main() resets (rt/main.cu:114-155) the frame is carried over
+    G_Buffer moved = {nullptr, nullptr, nullptr, nullptr};
+    if (!reproject_to.empty()) {
+        Camera camera2 = camera;
+        if (sscanf(reproject_to.c_str(), "%f %f %f %f %f", &camera2.position.x, &camera2.position.y,
+                   &camera2.position.z, &camera2.yaw, &camera2.pitch) != 5) {
+            usage();
+            return 2;
+        }
+        const size_t n = (size_t)width * height;
+        RtAovBuffers old_aov = {nullptr, nullptr, nullptr, nullptr};
+        free_aovs(&aov_buffers); // (the first camera's: the denoised frame is the second camera's)
+        if (render_guides(prepared, camera, width, height, &old_aov) != 0) return 1;
+        if (render_guides(prepared, camera2, width, height, &aov_buffers) != 0) return 1;
+        if (rt_device_alloc((void **)&moved.frame_buffer, n * 12) != RT_OK ||
+            rt_device_alloc((void **)&moved.squared_luminance, n * 4) != RT_OK ||
+            rt_device_alloc((void **)&moved.sample_count, n * 4) != RT_OK)
+            return fail("reprojected G_Buffer");
+        moved.random_numbers = g_buffer.random_numbers; // the per-pixel streams continue
+        if (rt_reproject(g_buffer, &old_aov, camera, &aov_buffers, camera2, width, height, moved, nullptr) != RT_OK)
+            return fail("reproject");
+        free_aovs(&old_aov);
+        for (int done = 0; done < spp2;) {
+            opt.passes = passes < spp2 - done ? passes : spp2 - done;
+            if (rt_render(prepared, moved, camera2, 1, &opt) != RT_OK) return fail("render after reprojection");
+            done += opt.passes;
+            if (!quiet) printf("samples per pixel after the move: +%d\n", done);
+        }
+        if (rt_synchronize() != RT_OK) return fail("synchronize");
+        camera = camera2;
+    }
+    const G_Buffer shown = moved.frame_buffer ? moved : g_buffer;
+    if (rt_save_render(shown, width, height, out.c_str()) != RT_OK) return fail("save_render");
     printf("rendered %dx%d x %d spp in %.3f s (%.2f Msamples/s nominal; scene setup %.2f s) -> %s\n", width, height,
            spp, render_s, (double)width * height * spp / render_s / 1e6, setup_s, out.c_str());
     if (denoise) {
         if (!aov_buffers.depth && render_aovs(prepared, camera, width, height, &aov_buffers) != 0) return 1;
         const std::string path = denoised_path(out);
-        if (write_denoised(g_buffer, aov_buffers, width, height, path) != 0) return 1;
+        if (write_denoised(shown, aov_buffers, width, height, path) != 0) return 1;
         if (!quiet) printf("denoised -> %s\n", path.c_str());
-        free_aovs(&aov_buffers);
+    }
+    free_aovs(&aov_buffers);
+    if (moved.frame_buffer) {
+        rt_free(moved.frame_buffer);
+        rt_free(moved.squared_luminance);
+        rt_free(moved.sample_count);
     }
 
     rt_scene_release(prepared);

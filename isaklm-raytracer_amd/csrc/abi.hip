@@ -16,8 +16,10 @@
 #include <string>
 #include <vector>
 
+#include "camera_math.h"
 #include "denoise_math.h"
 #include "host/rt_host.h"
+#include "reproject_math.h"
 
 int rt_launch_path(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera &cam, int stack_depth,
                    hipStream_t stream, int traversal);
@@ -50,6 +52,13 @@ int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const 
                       hipStream_t stream);
 int rt_launch_tonemap_rgb(const float *rgb, RtUChar4 *out, int n, hipStream_t stream);
 void rt_denoise_shutdown();
+// reproject.hip; the overlap rule: host/reproject_host.cpp
+int rt_launch_reproject(const RtRpFrame &src, const RtDevCamera &src_cam, const float *dst_depth,
+                        const float *dst_normal, const int *dst_triangle, const RtDevCamera &dst_cam, int width,
+                        int height, const RtRpParams &prm, Vec3D *fb_out, float *sq_out, int *count_out,
+                        unsigned long long *stats, hipStream_t stream);
+bool rt_rp_frames_overlap(const void *src_fb, const void *src_sq, const void *src_count, const void *dst_fb,
+                          const void *dst_sq, const void *dst_count, size_t n);
 
 static thread_local std::string g_error;
 
@@ -805,19 +814,8 @@ void rt_default_options(RtOptions *o)
     o->max_depth = 0;
 }
 
-// Camera::rotation() and tanf(FOV / 2) are frame constants (rt/camera.cuh:22-25, :381)
-static RtDevCamera device_camera(const Camera &cam)
-{
-    RtDevCamera dc;
-    RtM3 R = rt_rotation_matrix(cam.yaw, cam.pitch);
-    dc.R[0] = R.i.x; dc.R[1] = R.i.y; dc.R[2] = R.i.z;
-    dc.R[3] = R.j.x; dc.R[4] = R.j.y; dc.R[5] = R.j.z;
-    dc.R[6] = R.k.x; dc.R[7] = R.k.y; dc.R[8] = R.k.z;
-    dc.pos[0] = cam.position.x; dc.pos[1] = cam.position.y; dc.pos[2] = cam.position.z;
-    dc.tan_half_fov = rt_tanf(cam.FOV / 2);
-    dc.aperture = cam.aperture_radius;
-    return dc;
-}
+// Camera::rotation() and tanf(FOV / 2) are frame constants (camera_math.h, shared with rt_reproject_host)
+static RtDevCamera device_camera(const Camera &cam) { return rt_device_camera(cam); }
 
 // render (rt/render.cuh:62-76)
 int rt_render(rt_scene_t scene, G_Buffer g, Camera cam, int sample_count, const RtOptions *opt)
@@ -1099,6 +1097,51 @@ int rt_denoise(G_Buffer g, const RtAovBuffers *aov, int width, int height, float
     if (rt_launch_denoise(g.frame_buffer, g.squared_luminance, g.sample_count, aov->depth, aov->normal, aov->albedo,
                           width, height, rgb_out, prm, stream) != 0) {
         rt_set_error("rt_denoise: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return RT_E_HIP;
+    }
+    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
+}
+
+// ---------------- temporal reprojection (reproject.hip; rt_reproject_host and the default options:
+// host/reproject_host.cpp) ----------------
+int rt_reproject(G_Buffer src, const RtAovBuffers *sa, Camera src_cam, const RtAovBuffers *da, Camera dst_cam, int width,
+                 int height, G_Buffer dst, const RtReprojectOptions *opt)
+{
+    RtRpParams prm;
+    if (!rt_rp_resolve(opt, &prm)) {
+        rt_set_error("rt_reproject: option out of range (max_history 1..%d, match_triangle -1..1, depth_tol finite "
+                     "and >= 0, normal_min in (-1, 1])", RT_RP_MAX_HISTORY);
+        return RT_E_INVALID;
+    }
+    if (!src.frame_buffer || !src.squared_luminance || !src.sample_count || !dst.frame_buffer ||
+        !dst.squared_luminance || !dst.sample_count || !sa || !da || !sa->depth || !sa->normal || !da->depth ||
+        !da->normal) {
+        rt_set_error("rt_reproject: null G_Buffer array or AOV buffer");
+        return RT_E_INVALID;
+    }
+    if (misaligned(sa->depth, 4) || misaligned(sa->normal, 4) || misaligned(sa->triangle, 4) ||
+        misaligned(da->depth, 4) || misaligned(da->normal, 4) || misaligned(da->triangle, 4) ||
+        misaligned(opt ? opt->stats_device : nullptr, 8)) {
+        rt_set_error("rt_reproject: misaligned buffer");
+        return RT_E_INVALID;
+    }
+    const int rc = frame_size_ok("rt_reproject", width, height, 1);
+    if (rc != RT_OK) return rc;
+    if (rt_rp_frames_overlap(src.frame_buffer, src.squared_luminance, src.sample_count, dst.frame_buffer,
+                             dst.squared_luminance, dst.sample_count, (size_t)width * height)) {
+        rt_set_error("rt_reproject: dst's arrays overlap src's (the call is a gather)");
+        return RT_E_INVALID;
+    }
+    hipStream_t stream = (hipStream_t)(opt ? opt->stream : nullptr);
+    const int jr = join_status(stream, "rt_reproject"); // chained renders' deep-path tails first, as rt_tonemap
+    if (jr != RT_OK) return jr;
+    rt_register_shutdown();
+    const RtRpFrame sf = {src.frame_buffer, src.squared_luminance, src.sample_count, sa->depth, sa->normal, sa->triangle};
+    if (rt_launch_reproject(sf, rt_rp_camera(src_cam), da->depth, da->normal, da->triangle, rt_rp_camera(dst_cam),
+                            width, height, prm, dst.frame_buffer, dst.squared_luminance, dst.sample_count,
+                            opt ? opt->stats_device : nullptr, stream) != 0) {
+        rt_set_error("rt_reproject: launch failed: %s", hipGetErrorString(hipGetLastError()));
         return RT_E_HIP;
     }
     if (!stream) HIPCHK(hipStreamSynchronize(nullptr));

@@ -35,6 +35,7 @@
 #include <mutex>
 
 #include "bvh_trace.h"
+#include "camera_math.h"
 #include "rt_kernels.h"
 
 #define RQ_BLOCK 256
@@ -58,15 +59,12 @@ using namespace rtk;
 
 namespace {
 
-// camera_ray (rt_kernels.h; rt/path_tracing.cuh:381-391) with both jitter
-// draws 0.5 and no aperture offset: the pixel centre's direction, the camera
-// position itself as the origin.  Draws nothing from the pixel's RNG.
+// the pixel centre's direction (camera_math.h rt_camera_centre_dir, the text
+// rt_reproject shares), the camera position itself as the origin
 __device__ __forceinline__ void camera_ray_centre(const RtDevCamera &cam, int half_w, int half_h, int x, int y,
                                                   Vec3D &ro, Vec3D &rd)
 {
-    const Vec3D dir = rt_normalize(rt_v3(cam.tan_half_fov * ((float)x + 0.5f - (float)half_w) / (float)half_w,
-                                         cam.tan_half_fov * ((float)y + 0.5f - (float)half_h) / (float)half_w, 1.0f));
-    rd = mat_mul(cam.R, dir);
+    rd = rt_camera_centre_dir(cam, half_w, half_h, x, y);
     ro = rt_v3(cam.pos[0], cam.pos[1], cam.pos[2]);
 }
 

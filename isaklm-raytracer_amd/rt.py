@@ -86,6 +86,11 @@ class RtDenoiseOptions(ctypes.Structure):
                 ("normal_log2", ctypes.c_int), ("demodulate", ctypes.c_int), ("stream", ctypes.c_void_p)]
 
 
+class RtReprojectOptions(ctypes.Structure):
+    _fields_ = [("max_history", ctypes.c_int), ("depth_tol", ctypes.c_float), ("normal_min", ctypes.c_float),
+                ("match_triangle", ctypes.c_int), ("stream", ctypes.c_void_p), ("stats_device", ctypes.c_void_p)]
+
+
 # RtRayHit (16 B) and RtRaySurface (80 B) as numpy record types
 RAY_HIT = np.dtype([("triangle", np.int32), ("bx", np.float32), ("by", np.float32), ("bz", np.float32)])
 RAY_SURFACE = np.dtype([("position", np.float32, 3), ("t", np.float32), ("normal", np.float32, 3),
@@ -252,6 +257,13 @@ def lib():
         L.rt_denoise.argtypes = [G_Buffer, ctypes.POINTER(RtAovBuffers), i, i, vp, ctypes.POINTER(RtDenoiseOptions)]
         L.rt_denoise_host.argtypes = [vp, vp, vp, vp, vp, vp, i, i, vp, ctypes.POINTER(RtDenoiseOptions)]
         L.rt_tonemap_rgb.argtypes = [vp, vp, i, i, vp]
+        if hasattr(L, "rt_reproject"):  # (added within ABI 12: an earlier ABI-12 library lacks it)
+            L.rt_default_reproject_options.argtypes = [ctypes.POINTER(RtReprojectOptions)]
+            L.rt_default_reproject_options.restype = None
+            L.rt_reproject.argtypes = [G_Buffer, ctypes.POINTER(RtAovBuffers), Camera, ctypes.POINTER(RtAovBuffers),
+                                       Camera, i, i, G_Buffer, ctypes.POINTER(RtReprojectOptions)]
+            L.rt_reproject_host.argtypes = [vp, vp, vp, vp, vp, vp, Camera, vp, vp, vp, Camera, i, i, vp, vp, vp, vp,
+                                            ctypes.POINTER(RtReprojectOptions)]
         L.rt_shutdown.restype = None
         L.rt_abi_version.restype = i
         if L.rt_abi_version() != ABI_VERSION:
@@ -788,6 +800,120 @@ def denoise_host(fb, sq, count, depth, normal, albedo, **options):
     check(lib().rt_denoise_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(depth), _ptr(normal),
                                 None if albedo is None else _ptr(albedo), W, H, _ptr(out), ctypes.byref(o)))
     return out
+
+
+# ---------------------------------------------------------------- temporal reprojection
+REPROJECT_STATS = ("pixels", "kept_pixels", "carried_samples")  # RtReprojectOptions.stats_device [0..2]
+
+
+def reproject_options(max_history=0, depth_tol=0.0, normal_min=0.0, match_triangle=True, stream=None, stats=None):
+    """RtReprojectOptions; 0 = the library default (max_history 64, depth_tol 0.02, normal_min 0.95);
+    match_triangle False carries history across triangle edges of one surface; stream: an integer hipStream_t;
+    stats: a device pointer to 3 u64 (REPROJECT_STATS; the call adds to them)."""
+    o = RtReprojectOptions()
+    o.max_history, o.depth_tol, o.normal_min = int(max_history), depth_tol, normal_min
+    o.match_triangle = 1 if match_triangle else -1
+    o.stream = stream
+    o.stats_device = stats
+    return o
+
+
+def reproject_device(g_src, aov_src_ptrs, cam_src, aov_dst_ptrs, cam_dst, width, height, g_dst, **options):
+    """rt_reproject on device memory: g_src, g_dst G_Buffer structs, aov_*_ptrs (depth, normal, triangle)
+    integer device pointers (triangle may be None)."""
+    bs = RtAovBuffers(_int_ptr(aov_src_ptrs[0]), _int_ptr(aov_src_ptrs[1]), None, _int_ptr(aov_src_ptrs[2]))
+    bd = RtAovBuffers(_int_ptr(aov_dst_ptrs[0]), _int_ptr(aov_dst_ptrs[1]), None, _int_ptr(aov_dst_ptrs[2]))
+    if "stats" in options:
+        options = dict(options, stats=_int_ptr(options["stats"]))
+    o = reproject_options(**options)
+    check(lib().rt_reproject(g_src, ctypes.byref(bs), cam_src, ctypes.byref(bd), cam_dst, width, height, g_dst,
+                             ctypes.byref(o)))
+
+
+_RP_AOVS = (("depth", np.float32, 1), ("normal", np.float32, 3), ("triangle", np.int32, 1))
+
+
+def reproject(gbuf_src, aov_src, cam_src, aov_dst, cam_dst, out=None, stats=False, **options):
+    """rt_reproject: carries gbuf_src (rendered at cam_src) over to cam_dst.  aov_src, aov_dst: the dicts
+    rt.render_aov returns for the two cameras (numpy arrays, uploaded here) or dicts of integer device
+    pointers; keys depth, normal and optionally triangle.  Fills `out` (its RNG states are left alone) or
+    returns a new GBuffer whose RNG states are gbuf_src's, so the per-pixel streams continue; with stats=True
+    returns (gbuf, dict of REPROJECT_STATS).  Options: reproject_options."""
+    W, H = gbuf_src.width, gbuf_src.height
+    n = W * H
+    L = lib()
+    if out is None:
+        out = GBuffer(W, H)
+        rng = np.zeros(n, dtype=np.uint32)
+        check(L.rt_download(_ptr(rng), gbuf_src.g.random_numbers, rng.nbytes))
+        check(L.rt_upload(out.g.random_numbers, _ptr(rng), rng.nbytes))
+    elif (out.width, out.height) != (W, H):
+        raise ValueError("out does not match the source frame's size")
+    st = np.zeros(3, dtype=np.uint64)
+    with _DeviceBytes(n * 4) as sd, _DeviceBytes(n * 12) as sn, _DeviceBytes(n * 4) as stri, \
+            _DeviceBytes(n * 4) as dd, _DeviceBytes(n * 12) as dn, _DeviceBytes(n * 4) as dtri, \
+            _DeviceBytes(st.nbytes) as d_st:
+        sides = []
+        for aov, bufs in ((aov_src, (sd, sn, stri)), (aov_dst, (dd, dn, dtri))):
+            ptrs = []
+            for (k, dtype, per), d in zip(_RP_AOVS, bufs):
+                a = aov.get(k)
+                if isinstance(a, np.ndarray):
+                    a = np.ascontiguousarray(a, dtype=dtype)
+                    if a.size != n * per:
+                        raise ValueError(f"aov[{k!r}] does not match the {W} x {H} frame")
+                    check(L.rt_upload(d, _ptr(a), a.nbytes))
+                    ptrs.append(d)
+                else:
+                    ptrs.append(a)
+            sides.append(ptrs)
+        if stats:
+            check(L.rt_memset(d_st, 0, st.nbytes))
+            options = dict(options, stats=d_st)
+        reproject_device(gbuf_src.g, sides[0], cam_src, sides[1], cam_dst, W, H, out.g, **options)
+        _synchronize_stream(options.get("stream"))
+        if stats:
+            check(L.rt_download(_ptr(st), d_st, st.nbytes))
+    return (out, dict(zip(REPROJECT_STATS, (int(v) for v in st)))) if stats else out
+
+
+def reproject_host(src_fb, src_sq, src_count, aov_src, cam_src, aov_dst, cam_dst, stats=False, **options):
+    """rt_reproject_host: rt_reproject's arithmetic on the CPU, bit-identical to the GPU.  src_fb (H, W, 3),
+    src_sq and src_count (H, W); aov_src, aov_dst: dicts with depth (H, W), normal (H, W, 3) and optionally
+    triangle (H, W); the frame size is taken from aov_dst's depth.  Returns (fb (H, W, 3) float32, sq (H, W)
+    float32, count (H, W) int32), with stats=True also a dict of REPROJECT_STATS."""
+    depth = np.ascontiguousarray(aov_dst["depth"], dtype=np.float32)
+    if depth.ndim != 2:
+        raise ValueError("depth must have shape (H, W)")
+    H, W = depth.shape
+    n = W * H
+
+    def arr(a, dtype, per):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.size != n * per:
+            raise ValueError("buffer does not match the frame size")
+        return a
+    fb, sq, count = arr(src_fb, np.float32, 3), arr(src_sq, np.float32, 1), arr(src_count, np.int32, 1)
+    sides = []
+    for aov in (aov_src, aov_dst):
+        tri = aov.get("triangle")
+        sides.append((arr(aov["depth"], np.float32, 1), arr(aov["normal"], np.float32, 3),
+                      None if tri is None else arr(tri, np.int32, 1)))
+    out_fb = np.zeros((H, W, 3), np.float32)
+    out_sq = np.zeros((H, W), np.float32)
+    out_count = np.zeros((H, W), np.int32)
+    st = np.zeros(3, dtype=np.uint64)
+    options.pop("stream", None)
+    o = reproject_options(**options)
+
+    def opt_ptr(a):
+        return None if a is None else _ptr(a)
+    (s_d, s_n, s_t), (d_d, d_n, d_t) = sides
+    check(lib().rt_reproject_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(s_d), _ptr(s_n), opt_ptr(s_t), cam_src,
+                                  _ptr(d_d), _ptr(d_n), opt_ptr(d_t), cam_dst, W, H, _ptr(out_fb), _ptr(out_sq),
+                                  _ptr(out_count), _ptr(st), ctypes.byref(o)))
+    out = (out_fb, out_sq, out_count)
+    return out + (dict(zip(REPROJECT_STATS, (int(v) for v in st))),) if stats else out
 
 
 def tonemap_rgb(rgb):
