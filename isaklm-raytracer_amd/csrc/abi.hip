@@ -20,18 +20,9 @@
 #include "denoise_math.h"
 #include "host/rt_host.h"
 #include "reproject_math.h"
+#include "rt_launch.h"
 
-int rt_launch_path(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera &cam, int stack_depth,
-                   hipStream_t stream, int traversal);
 int rt_launch_tonemap(const Vec3D *fb, const int *count, RtUChar4 *out, int n, hipStream_t stream);
-int rt_launch_wavefront(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera &cam, hipStream_t stream,
-                        int variant, int tail, int finish_waves, int profile, int cap, int postpone, int wide,
-                        int pipes, int long_depth, int traversal, int overlap, int check_interval, int debug,
-                        int coalesce);
-
-int rt_wavefront_device_init();
-int rt_wavefront_join(void *stream, int consume);
-void rt_wavefront_shutdown();
 void rt_path_shutdown();
 // query.hip
 int rt_launch_trace_rays(const RtDevScene &sc, const float *rays, long long n, void *hits, void *surface, int traversal,
@@ -80,8 +71,6 @@ void rt_set_error(const char *fmt, ...)
             return RT_E_HIP;                                                                         \
         }                                                                                            \
     } while (0)
-
-const char *rt_wavefront_incomplete_msg();
 
 // rt_wavefront_join with the ABI's status: RT_E_INCOMPLETE when the join's
 // hand-off check found stranded pixels (a chained render's frame misses
@@ -865,10 +854,7 @@ int rt_render(rt_scene_t scene, G_Buffer g, Camera cam, int sample_count, const 
 
     hipStream_t stream = (hipStream_t)o.stream;
     if (o.kernel >= RT_KERNEL_WAVEFRONT && o.kernel <= 3) {
-        if (scene->max_depth > RT_STACK_DEPTH ||
-            rt_launch_wavefront(scene->dev, fr, dc, stream, o.kernel, o.wf_tail, o.wf_finish_waves, o.profile,
-                                o.wf_descent_cap, o.wf_postpone, o.wf_wide, o.wf_pipelines, o.wf_long_depth,
-                                o.traversal, o.overlap, o.check_interval, o.debug, o.coalesce_passes) != 0) {
+        if (scene->max_depth > RT_STACK_DEPTH || rt_launch_wavefront(scene->dev, fr, dc, o) != 0) {
             rt_set_error("rt_render: wavefront launch failed: %s", hipGetErrorString(hipGetLastError()));
             return RT_E_HIP;
         }

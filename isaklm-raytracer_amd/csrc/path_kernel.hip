@@ -24,6 +24,7 @@
 
 #include "bvh_trace.h"
 #include "rt_kernels.h"
+#include "rt_launch.h"
 
 #define RT_BLOCK 256
 #ifndef RT_MEGA_BVH_LDS

@@ -32,15 +32,6 @@ RT_HD float rt_square(float x) { return x * x; }                                
 RT_HD float rt_clamp(float x, float lo, float hi) { return fmaxf(lo, fminf(hi, x)); } // :22-25
 RT_HD float rt_mod(float x, float m) { return x - m * floorf(x / m); }            // :32-35
 
-// Correctly rounded n / d for a fixed d from its reciprocal (Markstein):
-// with y = RN(1/d), q0 = RN(n*y) is within 1 ulp of n/d, the residual
-// e = n - d*q0 is exact in one fma, and RN(q0 + e*y) = RN(n/d) — the same
-// bits as the IEEE division the reference performs, in 3 VALU ops instead of
-// the ~10 of a full division.  Valid without over/underflow, which the range
-// guards (|n|, |d| in [2^-60, 2^40]) ensure; outside them (axis-parallel rays,
-// origins on a split plane) the plain division runs.  Used for the KD split
-// distance t = (split - o) / d, whose d is one of the ray's 3 components.
-// tests/test_host.py::test_division_matches_ieee checks it against '/'.
 // The barycentric range test of intersect_triangle (rt/trace_ray.cuh:97-110):
 // every coordinate in [0, 1].  On the device as IEEE minimum / maximum
 // (v_minimum3_f32 / v_maximum3_f32): they propagate a NaN, which then fails
@@ -56,6 +47,15 @@ RT_HD bool rt_bary_inside(float cx, float cy, float cz)
 #endif
 }
 
+// Correctly rounded n / d for a fixed d from its reciprocal (Markstein):
+// with y = RN(1/d), q0 = RN(n*y) is within 1 ulp of n/d, the residual
+// e = n - d*q0 is exact in one fma, and RN(q0 + e*y) = RN(n/d) — the same
+// bits as the IEEE division the reference performs, in 3 VALU ops instead of
+// the ~10 of a full division.  Valid without over/underflow, which the range
+// guards (|n|, |d| in [2^-60, 2^40]) ensure; outside them (axis-parallel rays,
+// origins on a split plane) the plain division runs.  Used for the KD split
+// distance t = (split - o) / d, whose d is one of the ray's 3 components.
+// tests/test_host.py::test_division_matches_ieee checks it against '/'.
 RT_HD float rt_recip_guard(float d)
 {
     const float a = fabsf(d);

@@ -108,6 +108,25 @@ def test_bounded_queue_path(scene):
     helpers.assert_bitwise(gpu, ref, what=f"{scene} bounded queue path")
 
 
+def test_bounded_queue_path_counted():
+    """The same queue path in a counting call (RT_TRAVERSAL_BOUNDED_COUNTED with
+    wf_tail = 1): the counting builds of wf_trace_bvh_dyn and of the queue's
+    other launches beside the bounded traversal, which no other test launches.
+    The bounded traversal is exact, so the frame is the oracle's bit for bit
+    and every ray finds the reference's hit: samples, rays and hits count as
+    the reference's do (the node and triangle counters count the bounded
+    traversal's own work instead)."""
+    run = helpers.GpuRun("room_small")
+    W, H, P = 48, 27, 3
+    gpu, gcnt, _ = run.render(W, H, P, count=True, kernel=rt.KERNEL_WAVEFRONT, wf_tail=1,
+                              traversal=rt.TRAVERSAL_BOUNDED_COUNTED)
+    ref, rcnt = helpers.oracle_render(run.path, W, H, P)
+    print("bounded counted queue path:", gcnt, "oracle:", rcnt)
+    helpers.assert_bitwise(gpu, ref, what="room_small bounded counted queue path")
+    for k in ("sample", "ray", "hit"):
+        assert gcnt[k] == rcnt[k], (k, gcnt, rcnt)
+
+
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("scene", ["room_small", "cornell_blob"])
 @pytest.mark.parametrize("long_depth,pipes", [(1, 3), (3, 1), (-1, 2)],
