@@ -21,33 +21,9 @@
 #include "host/rt_host.h"
 #include "reproject_math.h"
 #include "rt_launch.h"
+#include "rt_workspace.h"
 
-int rt_launch_tonemap(const Vec3D *fb, const int *count, RtUChar4 *out, int n, hipStream_t stream);
-void rt_path_shutdown();
-// query.hip
-int rt_launch_trace_rays(const RtDevScene &sc, const float *rays, long long n, void *hits, void *surface, int traversal,
-                         unsigned long long *stats, hipStream_t stream);
-int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width, int height, float *depth,
-                         float *normal, float *albedo, int *triangle, int traversal, unsigned long long *stats,
-                         hipStream_t stream);
-int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *rays, hipStream_t stream);
-int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tmax, long long n, uint8_t *occluded,
-                       int traversal, unsigned long long *stats, hipStream_t stream);
-int rt_launch_trace_paths(const RtDevScene &sc, const float *rays, uint32_t *rng, long long n, float *radiance, float *sq,
-                          int samples, int max_depth, int accumulate, int traversal, unsigned long long *stats,
-                          hipStream_t stream);
-void rt_query_shutdown();
-// denoise.hip
-int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const float *depth, const float *normal,
-                      const float *albedo, int width, int height, float *rgb_out, const RtDnParams &prm,
-                      hipStream_t stream);
-int rt_launch_tonemap_rgb(const float *rgb, RtUChar4 *out, int n, hipStream_t stream);
-void rt_denoise_shutdown();
-// reproject.hip; the overlap rule: host/reproject_host.cpp
-int rt_launch_reproject(const RtRpFrame &src, const RtDevCamera &src_cam, const float *dst_depth,
-                        const float *dst_normal, const int *dst_triangle, const RtDevCamera &dst_cam, int width,
-                        int height, const RtRpParams &prm, Vec3D *fb_out, float *sq_out, int *count_out,
-                        unsigned long long *stats, hipStream_t stream);
+// host/reproject_host.cpp: the overlap rule
 bool rt_rp_frames_overlap(const void *src_fb, const void *src_sq, const void *src_count, const void *dst_fb,
                           const void *dst_sq, const void *dst_count, size_t n);
 
@@ -86,6 +62,15 @@ static int join_status(void *stream, const char *who, int consume = 1)
     }
     rt_set_error("%s: join: %s", who, hipGetErrorString(hipGetLastError()));
     return RT_E_HIP;
+}
+
+// the tail of every entry point that launches: the launcher's status (the HIP error's text with it), and a
+// call on the null stream returns with its work done
+static int launch_done(const char *who, int launch, hipStream_t stream)
+{
+    if (launch != 0) { rt_set_error("%s: launch failed: %s", who, hipGetErrorString(hipGetLastError())); return RT_E_HIP; }
+    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return RT_OK;
 }
 
 struct RtPreparedScene {
@@ -200,25 +185,22 @@ int upload_prepared(const rt_host::PreparedHost &h, int ntris, int nindices, rt_
     return RT_OK;
 }
 
-// always-on deviation statistics (RT_DEV_*), one zeroed block per device
-std::mutex g_dev_mu;
-std::map<int, unsigned long long *> g_dev_stats;
+// always-on deviation statistics (RT_DEV_*), one zeroed block per device (never replaced: no event)
+DeviceSlots<unsigned long long *> g_dev_stats;
 
 unsigned long long *dev_stats_block()
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> g(g_dev_mu);
-    auto it = g_dev_stats.find(dev);
-    if (it != g_dev_stats.end()) return it->second;
+    std::lock_guard<std::mutex> g(g_dev_stats.mu);
+    unsigned long long **slot = g_dev_stats.current();
+    if (!slot) return nullptr;
+    if (*slot) return *slot;
     void *p = nullptr;
     if (hipMalloc(&p, RT_DEV_WORDS * 8) != hipSuccess) return nullptr;
     if (hipMemset(p, 0, RT_DEV_WORDS * 8) != hipSuccess) {
         (void)hipFree(p);
         return nullptr;
     }
-    g_dev_stats[dev] = (unsigned long long *)p;
-    return (unsigned long long *)p;
+    return *slot = (unsigned long long *)p;
 }
 
 } // namespace
@@ -245,11 +227,7 @@ void rt_shutdown(void)
     rt_path_shutdown();
     rt_query_shutdown();
     rt_denoise_shutdown();
-    std::lock_guard<std::mutex> g(g_dev_mu);
-    for (auto &kv : g_dev_stats) {
-        if (hipSetDevice(kv.first) == hipSuccess) (void)hipFree(kv.second);
-    }
-    g_dev_stats.clear();
+    g_dev_stats.shutdown([](unsigned long long *&p) { (void)hipFree(p); });
 }
 
 int rt_join(void *stream) { return join_status(stream, "rt_join"); }
@@ -420,6 +398,15 @@ int rt_gbuffer_seeds(uint32_t *out, size_t count, uint64_t skip)
     return RT_OK;
 }
 
+static void gbuffer_free(G_Buffer *g)
+{
+    (void)hipFree(g->frame_buffer);
+    (void)hipFree(g->squared_luminance);
+    (void)hipFree(g->sample_count);
+    (void)hipFree(g->random_numbers);
+    memset(g, 0, sizeof *g);
+}
+
 int rt_gbuffer_create(int w, int h, uint64_t skip, G_Buffer *g)
 {
     if (!g || w <= 0 || h <= 0) { rt_set_error("rt_gbuffer_create: bad arguments"); return RT_E_INVALID; }
@@ -427,26 +414,26 @@ int rt_gbuffer_create(int w, int h, uint64_t skip, G_Buffer *g)
     memset(g, 0, sizeof *g);
     std::vector<uint32_t> seeds(n);
     rt_host::mt19937_seeds(seeds.data(), n, skip);
-    HIPCHK(hipMalloc((void **)&g->frame_buffer, n * sizeof(Vec3D)));
-    HIPCHK(hipMalloc((void **)&g->squared_luminance, n * sizeof(float)));
-    HIPCHK(hipMalloc((void **)&g->sample_count, n * sizeof(int)));
-    HIPCHK(hipMalloc((void **)&g->random_numbers, n * sizeof(uint32_t)));
-    HIPCHK(hipMemset(g->frame_buffer, 0, n * sizeof(Vec3D)));
-    HIPCHK(hipMemset(g->squared_luminance, 0, n * sizeof(float)));
-    HIPCHK(hipMemset(g->sample_count, 0, n * sizeof(int)));
-    HIPCHK(hipMemcpy(g->random_numbers, seeds.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return RT_OK;
+    const int rc = [&]() -> int {
+        HIPCHK(hipMalloc((void **)&g->frame_buffer, n * sizeof(Vec3D)));
+        HIPCHK(hipMalloc((void **)&g->squared_luminance, n * sizeof(float)));
+        HIPCHK(hipMalloc((void **)&g->sample_count, n * sizeof(int)));
+        HIPCHK(hipMalloc((void **)&g->random_numbers, n * sizeof(uint32_t)));
+        HIPCHK(hipMemset(g->frame_buffer, 0, n * sizeof(Vec3D)));
+        HIPCHK(hipMemset(g->squared_luminance, 0, n * sizeof(float)));
+        HIPCHK(hipMemset(g->sample_count, 0, n * sizeof(int)));
+        HIPCHK(hipMemcpy(g->random_numbers, seeds.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return RT_OK;
+    }();
+    if (rc != RT_OK) gbuffer_free(g); // what the failing path had allocated; *g zeroed again
+    return rc;
 }
 
 int rt_gbuffer_destroy(G_Buffer *g)
 {
     if (!g) return RT_E_INVALID;
     (void)rt_wavefront_join(nullptr, 0); // (a chained render's tail may still write it)
-    (void)hipFree(g->frame_buffer);
-    (void)hipFree(g->squared_luminance);
-    (void)hipFree(g->sample_count);
-    (void)hipFree(g->random_numbers);
-    memset(g, 0, sizeof *g);
+    gbuffer_free(g);
     return RT_OK;
 }
 
@@ -594,6 +581,15 @@ int rt_build_kd_tree(const Triangle *tris, int n, KD_Tree_Node **nodes_out, int 
 static std::mutex g_tex_mu;
 static std::map<const void *, std::vector<void *>> g_scene_textures;
 
+static void scene_free(Scene *s)
+{
+    (void)hipFree(s->triangles);
+    (void)hipFree(s->light_indicies);
+    (void)hipFree(s->kd_tree.nodes);
+    (void)hipFree(s->kd_tree.triangle_indicies);
+    memset(s, 0, sizeof *s);
+}
+
 int rt_create_scene(const RtHostScene *s, Scene *out, int *node_count, int *index_count)
 {
     if (!s || !out || s->tris.empty()) { rt_set_error("rt_create_scene: bad arguments"); return RT_E_INVALID; }
@@ -604,48 +600,58 @@ int rt_create_scene(const RtHostScene *s, Scene *out, int *node_count, int *inde
     Bounding_Box bb;
     int rc = rt_host::build_kd_tree(s->tris.data(), n, nodes, idx, bb);
     if (rc) return rc;
-    std::vector<int> lights = rt_host::light_list(s->tris.data(), n);
-    HIPCHK(hipMalloc((void **)&out->triangles, (size_t)n * sizeof(Triangle)));
-    if (s->textures.empty()) {
-        HIPCHK(hipMemcpy(out->triangles, s->tris.data(), (size_t)n * sizeof(Triangle), hipMemcpyHostToDevice));
-    } else {
-        // make_texture's cudaMalloc/cudaMemcpy (rt/scene.cuh:58-59): one device
-        // copy per decoded texture (with its zero pad), triangles re-pointed to it
-        std::map<const void *, RtUChar4 *> dev;
-        std::vector<void *> owned;
-        for (const auto &t : s->textures) {
-            RtUChar4 *d = nullptr;
-            const size_t bytes = t->texels.size() * sizeof(RtUChar4);
-            HIPCHK(hipMalloc((void **)&d, bytes));
-            owned.push_back(d);
-            HIPCHK(hipMemcpy(d, t->texels.data(), bytes, hipMemcpyHostToDevice));
-            dev[t->texels.data()] = d;
-        }
-        std::vector<Triangle> tris(s->tris);
-        for (Triangle &t : tris)
-            if (t.material.texture.buffer) {
-                auto it = dev.find(t.material.texture.buffer);
-                if (it == dev.end()) {
-                    rt_set_error("rt_create_scene: triangle texture not owned by the host scene");
-                    for (void *d : owned) (void)hipFree(d);
-                    return RT_E_INVALID;
-                }
-                t.material.texture.buffer = it->second;
+    const std::vector<int> lights = rt_host::light_list(s->tris.data(), n);
+    std::vector<void *> owned; // the textures' device copies
+    rc = [&]() -> int {
+        HIPCHK(hipMalloc((void **)&out->triangles, (size_t)n * sizeof(Triangle)));
+        if (s->textures.empty()) {
+            HIPCHK(hipMemcpy(out->triangles, s->tris.data(), (size_t)n * sizeof(Triangle), hipMemcpyHostToDevice));
+        } else {
+            // make_texture's cudaMalloc/cudaMemcpy (rt/scene.cuh:58-59): one device
+            // copy per decoded texture (with its zero pad), triangles re-pointed to it
+            std::map<const void *, RtUChar4 *> dev;
+            for (const auto &t : s->textures) {
+                RtUChar4 *d = nullptr;
+                const size_t bytes = t->texels.size() * sizeof(RtUChar4);
+                HIPCHK(hipMalloc((void **)&d, bytes));
+                owned.push_back(d);
+                HIPCHK(hipMemcpy(d, t->texels.data(), bytes, hipMemcpyHostToDevice));
+                dev[t->texels.data()] = d;
             }
-        HIPCHK(hipMemcpy(out->triangles, tris.data(), (size_t)n * sizeof(Triangle), hipMemcpyHostToDevice));
+            std::vector<Triangle> tris(s->tris);
+            for (Triangle &t : tris)
+                if (t.material.texture.buffer) {
+                    auto it = dev.find(t.material.texture.buffer);
+                    if (it == dev.end()) {
+                        rt_set_error("rt_create_scene: triangle texture not owned by the host scene");
+                        return RT_E_INVALID;
+                    }
+                    t.material.texture.buffer = it->second;
+                }
+            HIPCHK(hipMemcpy(out->triangles, tris.data(), (size_t)n * sizeof(Triangle), hipMemcpyHostToDevice));
+        }
+        out->triangle_count = n;
+        HIPCHK(hipMalloc((void **)&out->light_indicies, (lights.size() + 1) * sizeof(int)));
+        if (!lights.empty())
+            HIPCHK(hipMemcpy(out->light_indicies, lights.data(), lights.size() * sizeof(int), hipMemcpyHostToDevice));
+        out->light_count = (int)lights.size();
+        HIPCHK(hipMalloc((void **)&out->kd_tree.nodes, nodes.size() * sizeof(KD_Tree_Node)));
+        HIPCHK(hipMemcpy(out->kd_tree.nodes, nodes.data(), nodes.size() * sizeof(KD_Tree_Node), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc((void **)&out->kd_tree.triangle_indicies, (idx.size() + 1) * sizeof(int)));
+        if (!idx.empty())
+            HIPCHK(hipMemcpy(out->kd_tree.triangle_indicies, idx.data(), idx.size() * sizeof(int),
+                             hipMemcpyHostToDevice));
+        return RT_OK;
+    }();
+    if (rc != RT_OK) { // what the failing path had allocated; *out zeroed again
+        for (void *d : owned) (void)hipFree(d);
+        scene_free(out);
+        return rc;
+    }
+    if (!owned.empty()) {
         std::lock_guard<std::mutex> g(g_tex_mu);
         g_scene_textures[out->triangles] = owned;
     }
-    out->triangle_count = n;
-    HIPCHK(hipMalloc((void **)&out->light_indicies, (lights.size() + 1) * sizeof(int)));
-    if (!lights.empty())
-        HIPCHK(hipMemcpy(out->light_indicies, lights.data(), lights.size() * sizeof(int), hipMemcpyHostToDevice));
-    out->light_count = (int)lights.size();
-    HIPCHK(hipMalloc((void **)&out->kd_tree.nodes, nodes.size() * sizeof(KD_Tree_Node)));
-    HIPCHK(hipMemcpy(out->kd_tree.nodes, nodes.data(), nodes.size() * sizeof(KD_Tree_Node), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&out->kd_tree.triangle_indicies, (idx.size() + 1) * sizeof(int)));
-    if (!idx.empty())
-        HIPCHK(hipMemcpy(out->kd_tree.triangle_indicies, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
     out->kd_tree.bounding_box = bb;
     if (node_count) *node_count = (int)nodes.size();
     if (index_count) *index_count = (int)idx.size();
@@ -663,11 +669,7 @@ int rt_destroy_scene(Scene *s)
             g_scene_textures.erase(it);
         }
     }
-    (void)hipFree(s->triangles);
-    (void)hipFree(s->light_indicies);
-    (void)hipFree(s->kd_tree.nodes);
-    (void)hipFree(s->kd_tree.triangle_indicies);
-    memset(s, 0, sizeof *s);
+    scene_free(s);
     return RT_OK;
 }
 
@@ -803,9 +805,6 @@ void rt_default_options(RtOptions *o)
     o->max_depth = 0;
 }
 
-// Camera::rotation() and tanf(FOV / 2) are frame constants (camera_math.h, shared with rt_reproject_host)
-static RtDevCamera device_camera(const Camera &cam) { return rt_device_camera(cam); }
-
 // render (rt/render.cuh:62-76)
 int rt_render(rt_scene_t scene, G_Buffer g, Camera cam, int sample_count, const RtOptions *opt)
 {
@@ -850,7 +849,8 @@ int rt_render(rt_scene_t scene, G_Buffer g, Camera cam, int sample_count, const 
         return RT_E_HIP;
     }
 
-    const RtDevCamera dc = device_camera(cam);
+    // Camera::rotation() and tanf(FOV / 2) are frame constants (camera_math.h, shared with rt_reproject_host)
+    const RtDevCamera dc = rt_device_camera(cam);
 
     hipStream_t stream = (hipStream_t)o.stream;
     if (o.kernel >= RT_KERNEL_WAVEFRONT && o.kernel <= 3) {
@@ -866,8 +866,7 @@ int rt_render(rt_scene_t scene, G_Buffer g, Camera cam, int sample_count, const 
             return RT_E_HIP;
         }
     }
-    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_render", 0, stream);
 }
 
 // ---------------- ray queries and first-hit AOVs (query.hip) ----------------
@@ -880,22 +879,34 @@ void rt_default_query_options(RtQueryOptions *o)
 
 static bool misaligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
+// (false: the error text is set; the caller returns RT_E_INVALID, or RT_E_UNSUPPORTED for the stack depth)
+static bool count_ok(const char *who, long long n)
+{
+    if (n >= 0 && n <= (1LL << 31) - 1) return true;
+    rt_set_error("%s: n = %lld out of [0, 2^31 - 1]", who, n);
+    return false;
+}
+static bool traversal_ok(const char *who, int t)
+{
+    if (t == RT_TRAVERSAL_BOUNDED || t == RT_TRAVERSAL_KD || t == RT_TRAVERSAL_BOUNDED_COUNTED) return true;
+    rt_set_error("%s: traversal %d", who, t);
+    return false;
+}
+static bool stack_depth_ok(const char *who, rt_scene_t scene)
+{
+    if (scene->max_depth <= RT_STACK_DEPTH) return true;
+    rt_set_error("%s: KD tree depth %d beyond the traversal stack (%d)", who, scene->max_depth, RT_STACK_DEPTH);
+    return false;
+}
+
 // the checks every query shares, before any GPU call
 static int query_options(const char *who, rt_scene_t scene, const RtQueryOptions *opt, RtQueryOptions *o)
 {
     if (opt) *o = *opt; else rt_default_query_options(o);
     if (!scene) { rt_set_error("%s: null scene", who); return RT_E_INVALID; }
-    if (o->traversal != RT_TRAVERSAL_BOUNDED && o->traversal != RT_TRAVERSAL_KD &&
-        o->traversal != RT_TRAVERSAL_BOUNDED_COUNTED) {
-        rt_set_error("%s: traversal %d", who, o->traversal);
-        return RT_E_INVALID;
-    }
+    if (!traversal_ok(who, o->traversal)) return RT_E_INVALID;
     if (misaligned(o->stats_device, 8)) { rt_set_error("%s: stats_device is not 8-byte aligned", who); return RT_E_INVALID; }
-    if (scene->max_depth > RT_STACK_DEPTH) {
-        rt_set_error("%s: KD tree depth %d beyond the traversal stack (%d)", who, scene->max_depth, RT_STACK_DEPTH);
-        return RT_E_UNSUPPORTED;
-    }
-    return RT_OK;
+    return stack_depth_ok(who, scene) ? RT_OK : RT_E_UNSUPPORTED;
 }
 
 int rt_trace_rays(rt_scene_t scene, const float *rays, long long n, RtRayHit *hits, RtRaySurface *surface,
@@ -904,7 +915,7 @@ int rt_trace_rays(rt_scene_t scene, const float *rays, long long n, RtRayHit *hi
     static_assert(sizeof(RtRayHit) == 16 && sizeof(RtRaySurface) == 80, "query records");
     RtQueryOptions o;
     if (!rays || !hits) { rt_set_error("rt_trace_rays: null rays or hits"); return RT_E_INVALID; }
-    if (n < 0 || n > (1LL << 31) - 1) { rt_set_error("rt_trace_rays: n = %lld out of [0, 2^31 - 1]", n); return RT_E_INVALID; }
+    if (!count_ok("rt_trace_rays", n)) return RT_E_INVALID;
     if (misaligned(rays, 8) || misaligned(hits, 16) || misaligned(surface, 16)) {
         rt_set_error("rt_trace_rays: misaligned pointer (rays 8 B, hits and surface 16 B)");
         return RT_E_INVALID;
@@ -914,12 +925,9 @@ int rt_trace_rays(rt_scene_t scene, const float *rays, long long n, RtRayHit *hi
     if (n == 0) return RT_OK;
     rt_register_shutdown();
     hipStream_t stream = (hipStream_t)o.stream;
-    if (rt_launch_trace_rays(scene->dev, rays, n, hits, surface, o.traversal, o.stats_device, stream) != 0) {
-        rt_set_error("rt_trace_rays: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return RT_E_HIP;
-    }
-    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_trace_rays",
+                       rt_launch_trace_rays(scene->dev, rays, n, hits, surface, o.traversal, o.stats_device, stream),
+                       stream);
 }
 
 int rt_occluded(rt_scene_t scene, const float *rays, const float *tmax, long long n, uint8_t *occluded,
@@ -927,7 +935,7 @@ int rt_occluded(rt_scene_t scene, const float *rays, const float *tmax, long lon
 {
     RtQueryOptions o;
     if (!rays || !occluded) { rt_set_error("rt_occluded: null rays or output"); return RT_E_INVALID; }
-    if (n < 0 || n > (1LL << 31) - 1) { rt_set_error("rt_occluded: n = %lld out of [0, 2^31 - 1]", n); return RT_E_INVALID; }
+    if (!count_ok("rt_occluded", n)) return RT_E_INVALID;
     if (misaligned(rays, 8) || misaligned(tmax, 4)) {
         rt_set_error("rt_occluded: misaligned pointer (rays 8 B, tmax 4 B)");
         return RT_E_INVALID;
@@ -937,12 +945,9 @@ int rt_occluded(rt_scene_t scene, const float *rays, const float *tmax, long lon
     if (n == 0) return RT_OK;
     rt_register_shutdown();
     hipStream_t stream = (hipStream_t)o.stream;
-    if (rt_launch_occluded(scene->dev, rays, tmax, n, occluded, o.traversal, o.stats_device, stream) != 0) {
-        rt_set_error("rt_occluded: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return RT_E_HIP;
-    }
-    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_occluded",
+                       rt_launch_occluded(scene->dev, rays, tmax, n, occluded, o.traversal, o.stats_device, stream),
+                       stream);
 }
 
 void rt_default_path_options(RtPathOptions *o)
@@ -960,7 +965,7 @@ int rt_trace_paths(rt_scene_t scene, const float *rays, uint32_t *rng, long long
     if (opt) o = *opt; else rt_default_path_options(&o);
     if (!scene) { rt_set_error("rt_trace_paths: null scene"); return RT_E_INVALID; }
     if (!rays || !rng || !radiance) { rt_set_error("rt_trace_paths: null rays, rng or radiance"); return RT_E_INVALID; }
-    if (n < 0 || n > (1LL << 31) - 1) { rt_set_error("rt_trace_paths: n = %lld out of [0, 2^31 - 1]", n); return RT_E_INVALID; }
+    if (!count_ok("rt_trace_paths", n)) return RT_E_INVALID;
     if (misaligned(rays, 8) || misaligned(rng, 4) || misaligned(radiance, 4) || misaligned(sq_luminance, 4) ||
         misaligned(o.stats_device, 8)) {
         rt_set_error("rt_trace_paths: misaligned pointer (rays and stats_device 8 B, rng, radiance and sq_luminance 4 B)");
@@ -972,25 +977,15 @@ int rt_trace_paths(rt_scene_t scene, const float *rays, uint32_t *rng, long long
                      o.samples, o.max_depth, o.accumulate);
         return RT_E_INVALID;
     }
-    if (o.traversal != RT_TRAVERSAL_BOUNDED && o.traversal != RT_TRAVERSAL_KD &&
-        o.traversal != RT_TRAVERSAL_BOUNDED_COUNTED) {
-        rt_set_error("rt_trace_paths: traversal %d", o.traversal);
-        return RT_E_INVALID;
-    }
+    if (!traversal_ok("rt_trace_paths", o.traversal)) return RT_E_INVALID;
     if (n == 0) return RT_OK;
-    if (scene->max_depth > RT_STACK_DEPTH) {
-        rt_set_error("rt_trace_paths: KD tree depth %d beyond the traversal stack (%d)", scene->max_depth, RT_STACK_DEPTH);
-        return RT_E_UNSUPPORTED;
-    }
+    if (!stack_depth_ok("rt_trace_paths", scene)) return RT_E_UNSUPPORTED;
     rt_register_shutdown();
     hipStream_t stream = (hipStream_t)o.stream;
-    if (rt_launch_trace_paths(scene->dev, rays, rng, n, radiance, sq_luminance, o.samples ? o.samples : 1, o.max_depth,
-                              o.accumulate, o.traversal, o.stats_device, stream) != 0) {
-        rt_set_error("rt_trace_paths: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return RT_E_HIP;
-    }
-    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_trace_paths",
+                       rt_launch_trace_paths(scene->dev, rays, rng, n, radiance, sq_luminance, o.samples ? o.samples : 1,
+                                             o.max_depth, o.accumulate, o.traversal, o.stats_device, stream),
+                       stream);
 }
 
 // (min_width 2: the camera's half width divides; the denoiser has no camera and takes a 1-pixel column)
@@ -1008,12 +1003,9 @@ int rt_camera_rays(Camera cam, int width, int height, float *rays, void *stream)
     if (!rays || misaligned(rays, 8)) { rt_set_error("rt_camera_rays: null or misaligned rays"); return RT_E_INVALID; }
     const int rc = frame_size_ok("rt_camera_rays", width, height);
     if (rc != RT_OK) return rc;
-    if (rt_launch_camera_rays(device_camera(cam), width, height, rays, (hipStream_t)stream) != 0) {
-        rt_set_error("rt_camera_rays: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return RT_E_HIP;
-    }
-    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_camera_rays",
+                       rt_launch_camera_rays(rt_device_camera(cam), width, height, rays, (hipStream_t)stream),
+                       (hipStream_t)stream);
 }
 
 int rt_render_aov(rt_scene_t scene, Camera cam, int width, int height, const RtAovBuffers *b, const RtQueryOptions *opt)
@@ -1031,13 +1023,10 @@ int rt_render_aov(rt_scene_t scene, Camera cam, int width, int height, const RtA
     if (!b->depth && !b->normal && !b->albedo && !b->triangle && !o.stats_device) return RT_OK; // nothing asked for
     rt_register_shutdown();
     hipStream_t stream = (hipStream_t)o.stream;
-    if (rt_launch_render_aov(scene->dev, device_camera(cam), width, height, b->depth, b->normal, b->albedo, b->triangle,
-                             o.traversal, o.stats_device, stream) != 0) {
-        rt_set_error("rt_render_aov: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return RT_E_HIP;
-    }
-    if (!o.stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_render_aov",
+                       rt_launch_render_aov(scene->dev, rt_device_camera(cam), width, height, b->depth, b->normal,
+                                            b->albedo, b->triangle, o.traversal, o.stats_device, stream),
+                       stream);
 }
 
 int rt_tonemap(G_Buffer g, uint8_t *rgba, int w, int h, void *stream)
@@ -1048,12 +1037,9 @@ int rt_tonemap(G_Buffer g, uint8_t *rgba, int w, int h, void *stream)
     }
     const int jr = join_status(stream, "rt_tonemap"); // chained renders' deep-path tails first
     if (jr != RT_OK) return jr;
-    if (rt_launch_tonemap(g.frame_buffer, g.sample_count, (RtUChar4 *)rgba, w * h, (hipStream_t)stream) != 0) {
-        rt_set_error("rt_tonemap: launch failed");
-        return RT_E_HIP;
-    }
-    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_tonemap",
+                       rt_launch_tonemap(g.frame_buffer, g.sample_count, (RtUChar4 *)rgba, w * h, (hipStream_t)stream),
+                       (hipStream_t)stream);
 }
 
 // ---------------- denoising (denoise.hip; rt_denoise_host and the default options: host/denoise_host.cpp) ----------------
@@ -1080,13 +1066,10 @@ int rt_denoise(G_Buffer g, const RtAovBuffers *aov, int width, int height, float
     const int jr = join_status(stream, "rt_denoise"); // chained renders' deep-path tails first, as rt_tonemap
     if (jr != RT_OK) return jr;
     rt_register_shutdown();
-    if (rt_launch_denoise(g.frame_buffer, g.squared_luminance, g.sample_count, aov->depth, aov->normal, aov->albedo,
-                          width, height, rgb_out, prm, stream) != 0) {
-        rt_set_error("rt_denoise: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return RT_E_HIP;
-    }
-    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_denoise",
+                       rt_launch_denoise(g.frame_buffer, g.squared_luminance, g.sample_count, aov->depth, aov->normal,
+                                         aov->albedo, width, height, rgb_out, prm, stream),
+                       stream);
 }
 
 // ---------------- temporal reprojection (reproject.hip; rt_reproject_host and the default options:
@@ -1124,14 +1107,12 @@ int rt_reproject(G_Buffer src, const RtAovBuffers *sa, Camera src_cam, const RtA
     if (jr != RT_OK) return jr;
     rt_register_shutdown();
     const RtRpFrame sf = {src.frame_buffer, src.squared_luminance, src.sample_count, sa->depth, sa->normal, sa->triangle};
-    if (rt_launch_reproject(sf, rt_rp_camera(src_cam), da->depth, da->normal, da->triangle, rt_rp_camera(dst_cam),
-                            width, height, prm, dst.frame_buffer, dst.squared_luminance, dst.sample_count,
-                            opt ? opt->stats_device : nullptr, stream) != 0) {
-        rt_set_error("rt_reproject: launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return RT_E_HIP;
-    }
-    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_reproject",
+                       rt_launch_reproject(sf, rt_rp_camera(src_cam), da->depth, da->normal, da->triangle,
+                                           rt_rp_camera(dst_cam), width, height, prm, dst.frame_buffer,
+                                           dst.squared_luminance, dst.sample_count, opt ? opt->stats_device : nullptr,
+                                           stream),
+                       stream);
 }
 
 int rt_tonemap_rgb(const float *rgb, uint8_t *rgba, int w, int h, void *stream)
@@ -1142,12 +1123,8 @@ int rt_tonemap_rgb(const float *rgb, uint8_t *rgba, int w, int h, void *stream)
     }
     const int rc = frame_size_ok("rt_tonemap_rgb", w, h, 1);
     if (rc != RT_OK) return rc;
-    if (rt_launch_tonemap_rgb(rgb, (RtUChar4 *)rgba, w * h, (hipStream_t)stream) != 0) {
-        rt_set_error("rt_tonemap_rgb: launch failed");
-        return RT_E_HIP;
-    }
-    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
-    return RT_OK;
+    return launch_done("rt_tonemap_rgb", rt_launch_tonemap_rgb(rgb, (RtUChar4 *)rgba, w * h, (hipStream_t)stream),
+                       (hipStream_t)stream);
 }
 
 // save_render (rt/save_render.cuh:25-67): tonemap on the GPU, flip rows, PNG

@@ -19,10 +19,9 @@
 // same time within 10 % — so it has no LDS tile.
 #include <hip/hip_runtime.h>
 
-#include <map>
-#include <mutex>
-
 #include "denoise_math.h"
+#include "rt_launch.h"
+#include "rt_workspace.h"
 
 #define DN_TILE_W 32
 #define DN_TILE_H 8
@@ -86,25 +85,21 @@ __global__ void __launch_bounds__(256) rt_tonemap_rgb_kernel(const Vec3D *rgb, R
 
 // One denoise workspace per device, sized to the last frame: the two
 // ping-pong state buffers, the packed guides and the depth slopes (52 B per
-// pixel).  One call at a time may use it: calls are ordered on it by an event
-// — each waits on its stream for the previous call, whatever stream that was
-// on — under the mutex until the call is enqueued (as QueryWorkspace,
-// query.hip).  A frame of another size waits for that event on the host before
-// the buffers are replaced.
+// pixel).  One call at a time may use it, in rt_workspace.h's order: a frame
+// of another size waits on the host for the last call before the buffers are
+// replaced.
 struct DenoiseWorkspace {
     RtDn4 *state[2] = {nullptr, nullptr};
     RtDn4 *guide = nullptr;
     float *slope = nullptr;
     size_t pixels = 0;
-    hipEvent_t last = nullptr;
-    bool recorded = false;
+    SerialEvent serial;
 };
-std::mutex g_denoise_mu;
-std::map<int, DenoiseWorkspace> g_denoise;
+DeviceSlots<DenoiseWorkspace> g_denoise;
 
 void free_buffers(DenoiseWorkspace &w)
 {
-    if (w.recorded) (void)hipEventSynchronize(w.last);
+    (void)w.serial.wait_host(); // the buffers' last user, on whatever stream
     if (w.state[0]) (void)hipFree(w.state[0]);
     if (w.state[1]) (void)hipFree(w.state[1]);
     if (w.guide) (void)hipFree(w.guide);
@@ -141,13 +136,11 @@ int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const 
                       const float *albedo, int width, int height, float *rgb_out, const RtDnParams &prm,
                       hipStream_t stream)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    std::lock_guard<std::mutex> g(g_denoise_mu);
-    DenoiseWorkspace &w = g_denoise[dev];
-    if (!w.last && hipEventCreateWithFlags(&w.last, hipEventDisableTiming) != hipSuccess) return -1;
-    if (!size_workspace(w, (size_t)width * height)) return -1;
-    if (w.recorded && hipStreamWaitEvent(stream, w.last, 0) != hipSuccess) return -1;
+    std::lock_guard<std::mutex> g(g_denoise.mu);
+    DenoiseWorkspace *slot = g_denoise.current();
+    if (!slot) return -1;
+    DenoiseWorkspace &w = *slot;
+    if (!size_workspace(w, (size_t)width * height) || !w.serial.wait_on(stream)) return -1;
     const dim3 block(DN_TILE_W, DN_TILE_H);
     // (a 1-D grid of tiles, row by row: up to 2^31 / 256 + width / 32 + height / 8 blocks, within the x limit)
     const int tiles_x = (width + DN_TILE_W - 1) / DN_TILE_W;
@@ -163,9 +156,7 @@ int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const 
             hipLaunchKernelGGL(dn_filter_kernel<true>, grid, block, 0, stream, in, w.guide, w.slope, width, height,
                                tiles_x, 1 << s, prm, (RtDn4 *)nullptr, albedo, rgb_out);
     }
-    if (hipGetLastError() != hipSuccess || hipEventRecord(w.last, stream) != hipSuccess) return -1;
-    w.recorded = true;
-    return 0;
+    return w.serial.record(stream) ? 0 : -1;
 }
 
 int rt_launch_tonemap_rgb(const float *rgb, RtUChar4 *out, int n, hipStream_t stream)
@@ -177,14 +168,8 @@ int rt_launch_tonemap_rgb(const float *rgb, RtUChar4 *out, int n, hipStream_t st
 
 void rt_denoise_shutdown()
 {
-    std::lock_guard<std::mutex> g(g_denoise_mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto &kv : g_denoise) {
-        if (hipSetDevice(kv.first) != hipSuccess) continue;
-        free_buffers(kv.second);
-        if (kv.second.last) (void)hipEventDestroy(kv.second.last);
-    }
-    g_denoise.clear();
-    (void)hipSetDevice(cur);
+    g_denoise.shutdown([](DenoiseWorkspace &w) {
+        free_buffers(w);
+        w.serial.destroy();
+    });
 }

@@ -19,12 +19,11 @@
 //  * KD stack (node, entry t) in LDS, [depth][lane] => conflict-free.
 #include <hip/hip_runtime.h>
 
-#include <map>
-#include <mutex>
-
 #include "bvh_trace.h"
+#include "path_event.h"
 #include "rt_kernels.h"
 #include "rt_launch.h"
+#include "rt_workspace.h"
 
 #define RT_BLOCK 256
 #ifndef RT_MEGA_BVH_LDS
@@ -64,12 +63,12 @@ __global__ void __launch_bounds__(RT_BLOCK, BOUNDED ? RT_MEGA_BVH_WAVES : (STACK
         t_start = realtime();
     }
 
-    uint32_t rng = 0;
+    PathState p; // (p.rng: the pixel's RNG state, carried from path to path)
     Vec3D fb = rt_v3(0.0f, 0.0f, 0.0f);
     float sq = 0.0f;
     int count = 0;
     if (valid) {
-        rng = fr.rng[pi];
+        p.rng = fr.rng[pi];
         if (!fr.reset) {
             fb = fr.fb[pi];
             sq = fr.sq[pi];
@@ -79,16 +78,7 @@ __global__ void __launch_bounds__(RT_BLOCK, BOUNDED ? RT_MEGA_BVH_WAVES : (STACK
 
     int passes_left = valid ? fr.passes : 0;
     bool have_path = false;
-    bool shadow = false;  // current query is an NEE shadow ray
-    bool inside = false;  // inside_medium
-    int prev_type = PRIMARY;
-    int depth = 0;
-    int light = 0;
     const int limit = fr.max_depth > 0 ? fr.max_depth : RT_WATCHDOG_BOUNCES;
-    Vec3D ro = rt_v3(0, 0, 0), rd = rt_v3(0, 0, 0); // ray being traced
-    Vec3D cont = rt_v3(0, 0, 0);                     // scattered direction waiting behind a shadow ray
-    Vec3D sn_normal = rt_v3(0, 0, 0), rp = rt_v3(0, 0, 0);
-    Vec3D T = rt_v3(1, 1, 1), L = rt_v3(0, 0, 0);
 
     while (true) {
         if (!have_path) {
@@ -98,13 +88,8 @@ __global__ void __launch_bounds__(RT_BLOCK, BOUNDED ? RT_MEGA_BVH_WAVES : (STACK
                     if (COUNT) c.v[RT_CNT_SKIP]++;
                     continue;
                 }
-                camera_ray(fr, cam, x, y, rng, ro, rd);
-                T = rt_v3(1.0f, 1.0f, 1.0f);
-                L = rt_v3(0.0f, 0.0f, 0.0f);
-                inside = false;
-                prev_type = PRIMARY;
-                depth = 0;
-                shadow = false;
+                camera_ray(fr, cam, x, y, p.rng, p.ro, p.rd);
+                path_begin(p, 0);
                 have_path = true;
                 if (COUNT) c.v[RT_CNT_SAMPLE]++;
                 break;
@@ -113,67 +98,34 @@ __global__ void __launch_bounds__(RT_BLOCK, BOUNDED ? RT_MEGA_BVH_WAVES : (STACK
         }
 
         bool finish = false;
-        if (!shadow && depth == limit) { // max_depth / watchdog
+        if (!p.shadow && p.depth == limit) { // max_depth / watchdog
             if (COUNT && fr.max_depth <= 0) c.v[RT_CNT_WATCHDOG]++;
             dev_record_cut(fr);
             finish = true;
         } else {
-            if (!shadow) ++depth;
+            if (!p.shadow) ++p.depth;
             float bx = 0.0f, by = 0.0f, bz = 0.0f;
-            const int hit = BOUNDED ? trace_bvh<false>(sc, ro, rd, bx, by, bz, stk, c)
-                                    : trace<COUNT>(sc, ro, rd, bx, by, bz, stk, c);
+            const int hit = BOUNDED ? trace_bvh<false>(sc, p.ro, p.rd, bx, by, bz, stk, c)
+                                    : trace<COUNT>(sc, p.ro, p.rd, bx, by, bz, stk, c);
             bool roulette = true;
-            if (!shadow) {
+            if (!p.shadow) {
                 if (hit < 0) {
                     finish = true; // miss: break without roulette (:303-306)
                     roulette = false;
                 } else {
                     Surface s;
-                    shade<COUNT>(sc, hit, bx, by, bz, rd, s, c);
-                    if (prev_type != DIFFUSE) L = L + s.emittance * T; // :285-288
-                    Vec3D nd, w;
-                    prev_type = scatter(rd, inside, rng, s, nd, w);
-                    T = T * w;
-                    ro = s.position;
-                    rd = nd;
-                    if (prev_type == DIFFUSE) { // sample_direct_light (:235-265)
-                        if (COUNT) c.v[RT_CNT_NEE]++;
-                        float xi = rng_next(rng);
-                        if (sc.light_count == 0) {
-                            rng_next(rng);
-                            rng_next(rng);
-                            L = L + rt_v3(0.0f, 0.0f, 0.0f) * T;
-                        } else {
-                            light = sc.lights[(int)(xi * (float)sc.light_count)];
-                            rp = light_point(sc, light, rng);
-                            cont = rd;
-                            sn_normal = s.normal;
-                            rd = rt_normalize(rp - ro);
-                            shadow = true;
-                            roulette = false; // roulette after the shadow ray
-                        }
-                    }
+                    if (path_bounce<COUNT>(sc, p, hit, bx, by, bz, s, c)) roulette = false; // ... after the shadow ray
                 }
             } else {
-                Vec3D direct = rt_v3(0.0f, 0.0f, 0.0f);
-                if (hit >= 0 && hit == light) direct = light_contribution(sc, light, bx, by, bz, ro, rd, rp, sn_normal);
-                if (COUNT && hit >= 0 && material_of(sc, hit).tex) c.v[RT_CNT_TEXEL] += 2; // every hit is shaded
-                L = L + direct * T;
-                rd = cont;
-                shadow = false;
+                path_shadow_result<COUNT>(sc, p, hit, bx, by, bz, c);
             }
-            if (roulette) { // Russian roulette (:309-318)
-                float p = fmaxf(T.x, fmaxf(T.y, T.z));
-                float r = rng_next(rng);
-                if (r > p) finish = true;
-                else T = T * (1.0f / p);
-            }
+            if (roulette && !path_roulette(p)) finish = true;
         }
         if (finish) { // accumulation (:322-324)
-            if (COUNT) c.path_end(depth);
-            dev_record_end(fr, depth);
-            fb = fb + L;
-            sq = sq + rt_square(rt_luminance(L));
+            if (COUNT) c.path_end(p.depth);
+            dev_record_end(fr, p.depth);
+            fb = fb + p.L;
+            sq = sq + rt_square(rt_luminance(p.L));
             ++count;
             have_path = false;
         }
@@ -183,7 +135,7 @@ __global__ void __launch_bounds__(RT_BLOCK, BOUNDED ? RT_MEGA_BVH_WAVES : (STACK
         fr.fb[pi] = fb;
         fr.sq[pi] = sq;
         fr.count[pi] = count;
-        fr.rng[pi] = rng;
+        fr.rng[pi] = p.rng;
     }
     if (COUNT) {
         flush_counters(c, fr.counters);
@@ -213,33 +165,24 @@ __global__ void __launch_bounds__(256) rt_tonemap_kernel(const Vec3D *fb, const 
 // ---- host launchers (called by abi.hip) ----
 namespace {
 // Per-device spill area of the bounded megakernel (grown on demand), indexed
-// by global thread id: one launch at a time may use it.  Launches are
-// serialised on it — each waits (on its stream) for the previous launch's
-// event, whatever stream that was on — and the buffer is replaced only after
-// that launch is done, all under the mutex until the launch is enqueued.
+// by global thread id: one launch at a time may use it, in rt_workspace.h's
+// order.
 struct MegaSpill {
     uint2 *buf = nullptr;
     size_t entries = 0;
-    hipEvent_t last = nullptr; // after the last launch that used buf
-    bool recorded = false;
+    SerialEvent serial;
 };
-std::mutex g_spill_mu;
-std::map<int, MegaSpill> g_spill;
+DeviceSlots<MegaSpill> g_spill;
+
+using PathKernel = void (*)(RtDevScene, RtDevFrame, RtDevCamera, uint2 *, int);
 } // namespace
 
 void rt_path_shutdown()
 {
-    std::lock_guard<std::mutex> g(g_spill_mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto &kv : g_spill) {
-        if (hipSetDevice(kv.first) != hipSuccess) continue;
-        if (kv.second.recorded) (void)hipEventSynchronize(kv.second.last);
-        if (kv.second.buf) (void)hipFree(kv.second.buf);
-        if (kv.second.last) (void)hipEventDestroy(kv.second.last);
-    }
-    g_spill.clear();
-    (void)hipSetDevice(cur);
+    g_spill.shutdown([](MegaSpill &m) {
+        m.serial.destroy();
+        if (m.buf) (void)hipFree(m.buf);
+    });
 }
 
 int rt_launch_path(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera &cam, int stack_depth,
@@ -253,44 +196,30 @@ int rt_launch_path(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera
         const size_t threads = (size_t)tiles * RT_BLOCK;
         const int deeper = (RT_BVH_STACK > RT_STACK_DEPTH ? RT_BVH_STACK : RT_STACK_DEPTH) - RT_MEGA_BVH_LDS;
         const size_t entries = threads * (size_t)deeper;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return -1;
-        std::lock_guard<std::mutex> g(g_spill_mu);
-        MegaSpill &m = g_spill[dev];
-        if (!m.last && hipEventCreateWithFlags(&m.last, hipEventDisableTiming) != hipSuccess) return -1;
-        if (m.entries < entries) {
-            if (m.recorded && hipEventSynchronize(m.last) != hipSuccess) return -1; // the old buffer's last user
-            if (m.buf) (void)hipFree(m.buf);
-            m.buf = nullptr;
-            m.entries = 0;
+        std::lock_guard<std::mutex> g(g_spill.mu);
+        MegaSpill *m = g_spill.current();
+        if (!m) return -1;
+        if (m->entries < entries) {
+            if (!m->serial.wait_host()) return -1; // the old buffer's last user
+            if (m->buf) (void)hipFree(m->buf);
+            m->buf = nullptr;
+            m->entries = 0;
             void *p = nullptr;
             if (hipMalloc(&p, entries * sizeof(uint2)) != hipSuccess) return -1;
-            m.buf = (uint2 *)p;
-            m.entries = entries;
-        } else if (m.recorded && hipStreamWaitEvent(stream, m.last, 0) != hipSuccess) {
-            return -1; // the previous launch (maybe on another stream) leaves the spill slots first
+            m->buf = (uint2 *)p;
+            m->entries = entries;
         }
-        hipLaunchKernelGGL((rt_path_kernel<false, RT_MEGA_BVH_LDS, true>), grid, block, 0, stream, sc, fr, cam, m.buf,
+        // the previous launch (maybe on another stream) leaves the spill slots first
+        if (!m->serial.wait_on(stream)) return -1;
+        hipLaunchKernelGGL((rt_path_kernel<false, RT_MEGA_BVH_LDS, true>), grid, block, 0, stream, sc, fr, cam, m->buf,
                            (int)threads);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(m.last, stream) != hipSuccess) return -1;
-        m.recorded = true;
-        return 0;
+        return m->serial.record(stream) ? 0 : -1;
     }
-    if (stack_depth <= RT_STACK_SMALL) {
-        if (count)
-            hipLaunchKernelGGL((rt_path_kernel<true, RT_STACK_SMALL, false>), grid, block, 0, stream, sc, fr, cam,
-                               nullptr, 0);
-        else
-            hipLaunchKernelGGL((rt_path_kernel<false, RT_STACK_SMALL, false>), grid, block, 0, stream, sc, fr, cam,
-                               nullptr, 0);
-    } else {
-        if (count)
-            hipLaunchKernelGGL((rt_path_kernel<true, RT_STACK_DEPTH, false>), grid, block, 0, stream, sc, fr, cam,
-                               nullptr, 0);
-        else
-            hipLaunchKernelGGL((rt_path_kernel<false, RT_STACK_DEPTH, false>), grid, block, 0, stream, sc, fr, cam,
-                               nullptr, 0);
-    }
+    static const PathKernel plain[2][2] = { // [count][small]
+        {rt_path_kernel<false, RT_STACK_DEPTH, false>, rt_path_kernel<false, RT_STACK_SMALL, false>},
+        {rt_path_kernel<true, RT_STACK_DEPTH, false>, rt_path_kernel<true, RT_STACK_SMALL, false>}};
+    hipLaunchKernelGGL(plain[count][stack_depth <= RT_STACK_SMALL], grid, block, 0, stream, sc, fr, cam,
+                       (uint2 *)nullptr, 0);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

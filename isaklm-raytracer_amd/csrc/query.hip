@@ -31,12 +31,12 @@
 // itself.  Either way the result is trace_ray's, bit for bit.
 #include <hip/hip_runtime.h>
 
-#include <map>
-#include <mutex>
-
 #include "bvh_trace.h"
 #include "camera_math.h"
+#include "path_event.h"
 #include "rt_kernels.h"
+#include "rt_launch.h"
+#include "rt_workspace.h"
 
 #define RQ_BLOCK 256
 #ifndef RQ_LDS
@@ -146,17 +146,47 @@ __device__ __forceinline__ bool direction_in_domain(Vec3D d)
     return (ax <= 2.0f && ay <= 2.0f && az <= 2.0f) && (ax >= 0.5f || ay >= 0.5f || az >= 0.5f);
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+// the domain gate (see the head of this file): whether the bounded traversal may take this ray
+__device__ __forceinline__ bool in_bounded_domain(const RtDevScene &sc, int kd_only, Vec3D o, Vec3D d)
 {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
+    return !kd_only && direction_in_domain(d) && rt_bounded_ray(o, d, sc.split_vals, sc.split_off);
 }
 
-__device__ __forceinline__ unsigned long long wave_sum64(uint32_t lane_count)
+// the closest hit of (o, d) by the bounded traversal inside the gate, by the plain KD traversal outside
+// it (ran_kd): trace_ray's result either way
+template <typename STACK>
+__device__ __forceinline__ int query_trace(const RtDevScene &sc, int kd_only, Vec3D o, Vec3D d, float &bx, float &by,
+                                           float &bz, STACK &stk, Cnt &c, bool &ran_kd)
 {
-    unsigned long long v = lane_count;
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
+    ran_kd = !in_bounded_domain(sc, kd_only, o, d);
+    if (ran_kd) return trace<false>(sc, o, d, bx, by, bz, stk, c);
+    return trace_bvh<false>(sc, o, d, bx, by, bz, stk, c);
+}
+
+// the next ray index for each lane that is here (the counter stops below n + the grid's threads: no wrap)
+__device__ __forceinline__ uint32_t wave_next_index(uint32_t *fetch, int lane)
+{
+    const unsigned long long m = __ballot(true);
+    const int leader = __ffsll((long long)m) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
+    base = __shfl(base, leader);
+    return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// stats[k] += the wave's sum of lane_counts[k], by lane 0 and only where the sum is not zero (every lane
+// of the wave calls this: the kernels' loop exits reconverge before it)
+template <int N>
+__device__ __forceinline__ void flush_stats(unsigned long long *stats, const uint32_t (&lane_counts)[N], int lane)
+{
+    unsigned long long total[N];
+    for (int k = 0; k < N; ++k) {
+        total[k] = lane_counts[k];
+        for (int off = 32; off > 0; off >>= 1) total[k] += __shfl_xor(total[k], off);
+    }
+    if (lane != 0) return;
+    for (int k = 0; k < N; ++k)
+        if (total[k]) atomicAdd(stats + k, total[k]);
 }
 
 // one ray's result into the sink: the hit record, and the surface (the renderer's shade()) if asked for
@@ -203,38 +233,19 @@ __global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
     const int lane = __lane_id();
     uint32_t n_rays = 0, n_hits = 0, n_kd = 0;
     while (true) {
-        const unsigned long long m = __ballot(true);
-        const int leader = __ffsll((long long)m) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
-        base = __shfl(base, leader);
-        const uint32_t e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (e >= n) break; // (the counter stops below n + the grid's threads <= 2^31 + 2^20: no wrap)
+        const uint32_t e = wave_next_index(fetch, lane);
+        if (e >= n) break;
         Vec3D o, d;
         src.load(e, o, d);
         float bx = 0.0f, by = 0.0f, bz = 0.0f;
-        int tri;
-        // the domain gate (see the head of this file)
-        if (!kd_only && direction_in_domain(d) && rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
-            tri = trace_bvh<false>(sc, o, d, bx, by, bz, stk, c);
-        } else {
-            tri = trace<false>(sc, o, d, bx, by, bz, stk, c);
-            ++n_kd;
-        }
+        bool ran_kd;
+        const int tri = query_trace(sc, kd_only, o, d, bx, by, bz, stk, c, ran_kd);
+        if (ran_kd) ++n_kd;
         ++n_rays;
         if (tri >= 0) ++n_hits;
         store_result(sc, sink, e, o, d, tri, bx, by, bz);
     }
-    if (stats) { // (every lane of the wave is here: the loop's exits reconverge)
-        n_rays = wave_sum(n_rays);
-        n_hits = wave_sum(n_hits);
-        n_kd = wave_sum(n_kd);
-        if (lane == 0) {
-            if (n_rays) atomicAdd(stats + 0, (unsigned long long)n_rays);
-            if (n_hits) atomicAdd(stats + 1, (unsigned long long)n_hits);
-            if (n_kd) atomicAdd(stats + 2, (unsigned long long)n_kd);
-        }
-    }
+    if (stats) flush_stats(stats, {n_rays, n_hits, n_kd}, lane);
 }
 
 // ---- the occlusion query (rt_occluded) ----
@@ -274,19 +285,14 @@ __global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
     const int lane = __lane_id();
     uint32_t n_rays = 0, n_occ = 0, n_kd = 0, n_early = 0;
     while (true) {
-        const unsigned long long m = __ballot(true);
-        const int leader = __ffsll((long long)m) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
-        base = __shfl(base, leader);
-        const uint32_t e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (e >= n) break; // (no wrap: as rt_query_kernel)
+        const uint32_t e = wave_next_index(fetch, lane);
+        if (e >= n) break;
         Vec3D o, d;
         float tmax;
         src.load(e, o, d, tmax);
         bool occ = false;
         if (tmax > 0.00001f) { // (false for a NaN)
-            if (!kd_only && direction_in_domain(d) && rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
+            if (in_bounded_domain(sc, kd_only, o, d)) {
                 bool early;
                 occ = occluded_bvh(sc, o, d, tmax, stk, c, early);
                 if (RQ_COUNT_EARLY && early) ++n_early;
@@ -300,19 +306,9 @@ __global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
         if (occ) ++n_occ;
         sink.store(e, occ);
     }
-    if (stats) { // (every lane of the wave is here: the loop's exits reconverge)
-        n_rays = wave_sum(n_rays);
-        n_occ = wave_sum(n_occ);
-        n_kd = wave_sum(n_kd);
-        if (lane == 0) {
-            if (n_rays) atomicAdd(stats + 0, (unsigned long long)n_rays);
-            if (n_occ) atomicAdd(stats + 1, (unsigned long long)n_occ);
-            if (n_kd) atomicAdd(stats + 2, (unsigned long long)n_kd);
-        }
-        if (RQ_COUNT_EARLY) {
-            n_early = wave_sum(n_early);
-            if (lane == 0 && n_early) atomicAdd(stats + 3, (unsigned long long)n_early);
-        }
+    if (stats) {
+        flush_stats(stats, {n_rays, n_occ, n_kd}, lane);
+        if (RQ_COUNT_EARLY) flush_stats(stats + 3, {n_early}, lane);
     }
 }
 
@@ -321,9 +317,10 @@ __global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
 // traced `samples` times from rng[e], started as the renderer starts a camera
 // ray (PRIMARY, outside every medium, throughput 1), and the sums of L and of
 // luminance(L)^2 (:322-324) go to radiance[e] / sq[e], the RNG state back to
-// rng[e].  The loop is rt_path_kernel's (path_kernel.hip): one ray query per
-// iteration from one place, extension and NEE shadow rays as two states of
-// it, the path state in registers.
+// rng[e].  The loop has rt_path_kernel's shape (path_kernel.hip) and runs the
+// same events (path_event.h): one ray query per iteration from one place,
+// extension and NEE shadow rays as two states of it, the path state in
+// registers.
 //
 // Regeneration is per lane: a lane whose path ends starts its ray's next
 // sample in the same iteration, and a lane whose ray is done stores it and
@@ -352,22 +349,13 @@ __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
     const int lane = __lane_id();
     uint32_t n_rays = 0, n_paths = 0, n_trace = 0, n_cut = 0, max_len = 0;
 
-    uint32_t e = 0, rng = 0;
+    uint32_t e = 0;
     bool have_ray = false, have_path = false;
     int samples_left = 0;
     Vec3D o0 = rt_v3(0, 0, 0), d0 = rt_v3(0, 0, 0); // the caller's ray
     Vec3D sum = rt_v3(0, 0, 0);
     float sum_sq = 0.0f;
-
-    bool shadow = false; // current query is an NEE shadow ray
-    bool inside = false; // inside_medium
-    int prev_type = PRIMARY;
-    int depth = 0;
-    int light = 0;
-    Vec3D ro = rt_v3(0, 0, 0), rd = rt_v3(0, 0, 0); // ray being traced
-    Vec3D cont = rt_v3(0, 0, 0);                     // scattered direction waiting behind a shadow ray
-    Vec3D sn_normal = rt_v3(0, 0, 0), rp = rt_v3(0, 0, 0);
-    Vec3D T = rt_v3(1, 1, 1), L = rt_v3(0, 0, 0);
+    PathState p; // (p.rng: the ray's RNG state, carried from sample to sample)
 
     while (true) {
         if (!have_path) {
@@ -378,19 +366,14 @@ __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
                     r[1] = sum.y;
                     r[2] = sum.z;
                     if (sq_out) sq_out[e] = sum_sq;
-                    rng_io[e] = rng;
+                    rng_io[e] = p.rng;
                     have_ray = false;
                 }
-                // the next ray, for the lanes that are here
-                const unsigned long long m = __ballot(true);
-                const int leader = __ffsll((long long)m) - 1;
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
-                base = __shfl(base, leader);
-                e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                if (e >= n) break; // (the counter stops below n + the grid's threads <= 2^31 + 2^20: no wrap)
+                const uint32_t next = wave_next_index(fetch, lane); // for the lanes that are here
+                if (next >= n) break;
+                e = next;
                 src.load(e, o0, d0);
-                rng = rng_io[e];
+                p.rng = rng_io[e];
                 sum = rt_v3(0.0f, 0.0f, 0.0f);
                 sum_sq = 0.0f;
                 if (accumulate) {
@@ -403,99 +386,52 @@ __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
                 ++n_rays;
             }
             --samples_left;
-            ro = o0;
-            rd = d0;
-            T = rt_v3(1.0f, 1.0f, 1.0f);
-            L = rt_v3(0.0f, 0.0f, 0.0f);
-            inside = false;
-            prev_type = PRIMARY;
-            depth = 0;
-            shadow = false;
+            p.ro = o0;
+            p.rd = d0;
+            path_begin(p, 0);
             have_path = true;
             ++n_paths;
         }
 
         bool finish = false;
-        if (!shadow && depth == limit) { // max_depth / watchdog
+        if (!p.shadow && p.depth == limit) { // max_depth / watchdog
             ++n_cut;
             finish = true;
         } else {
-            if (!shadow) ++depth;
+            if (!p.shadow) ++p.depth;
             ++n_trace;
             float bx = 0.0f, by = 0.0f, bz = 0.0f;
-            int hit;
-            // the domain gate (see the head of this file)
-            if (!kd_only && direction_in_domain(rd) && rt_bounded_ray(ro, rd, sc.split_vals, sc.split_off))
-                hit = trace_bvh<false>(sc, ro, rd, bx, by, bz, stk, c);
-            else
-                hit = trace<false>(sc, ro, rd, bx, by, bz, stk, c);
+            bool ran_kd;
+            const int hit = query_trace(sc, kd_only, p.ro, p.rd, bx, by, bz, stk, c, ran_kd);
             bool roulette = true;
-            if (!shadow) {
+            if (!p.shadow) {
                 if (hit < 0) {
                     finish = true; // miss: break without roulette (:303-306)
                     roulette = false;
                 } else {
                     Surface s;
-                    shade<false>(sc, hit, bx, by, bz, rd, s, c);
-                    if (prev_type != DIFFUSE) L = L + s.emittance * T; // :285-288
-                    Vec3D nd, w;
-                    prev_type = scatter(rd, inside, rng, s, nd, w);
-                    T = T * w;
-                    ro = s.position;
-                    rd = nd;
-                    if (prev_type == DIFFUSE) { // sample_direct_light (:235-265)
-                        float xi = rng_next(rng);
-                        if (sc.light_count == 0) {
-                            rng_next(rng);
-                            rng_next(rng);
-                            L = L + rt_v3(0.0f, 0.0f, 0.0f) * T;
-                        } else {
-                            light = sc.lights[(int)(xi * (float)sc.light_count)];
-                            rp = light_point(sc, light, rng);
-                            cont = rd;
-                            sn_normal = s.normal;
-                            rd = rt_normalize(rp - ro);
-                            shadow = true;
-                            roulette = false; // roulette after the shadow ray
-                        }
-                    }
+                    if (path_bounce<false>(sc, p, hit, bx, by, bz, s, c)) roulette = false; // ... after the shadow ray
                 }
             } else {
-                Vec3D direct = rt_v3(0.0f, 0.0f, 0.0f);
-                if (hit >= 0 && hit == light) direct = light_contribution(sc, light, bx, by, bz, ro, rd, rp, sn_normal);
-                L = L + direct * T;
-                rd = cont;
-                shadow = false;
+                path_shadow_result<false>(sc, p, hit, bx, by, bz, c);
             }
-            if (roulette) { // Russian roulette (:309-318)
-                float p = fmaxf(T.x, fmaxf(T.y, T.z));
-                float r = rng_next(rng);
-                if (r > p) finish = true;
-                else T = T * (1.0f / p);
-            }
+            if (roulette && !path_roulette(p)) finish = true;
         }
         if (finish) { // accumulation (:322-324)
-            sum = sum + L;
-            sum_sq = sum_sq + rt_square(rt_luminance(L));
-            max_len = (uint32_t)depth > max_len ? (uint32_t)depth : max_len;
+            sum = sum + p.L;
+            sum_sq = sum_sq + rt_square(rt_luminance(p.L));
+            max_len = (uint32_t)p.depth > max_len ? (uint32_t)p.depth : max_len;
             have_path = false;
         }
     }
 
-    if (stats) { // (every lane of the wave is here: the loop's exits reconverge)
-        const unsigned long long rays = wave_sum64(n_rays), paths = wave_sum64(n_paths), calls = wave_sum64(n_trace),
-                                 cuts = wave_sum64(n_cut);
+    if (stats) {
+        flush_stats(stats, {n_rays, n_paths, n_trace, n_cut}, lane);
         for (int off = 32; off > 0; off >>= 1) {
             const uint32_t other = __shfl_xor(max_len, off);
             max_len = other > max_len ? other : max_len;
         }
-        if (lane == 0) {
-            if (rays) atomicAdd(stats + 0, rays);
-            if (paths) atomicAdd(stats + 1, paths);
-            if (calls) atomicAdd(stats + 2, calls);
-            if (cuts) atomicAdd(stats + 3, cuts);
-            if (max_len) atomicMax(stats + 4, (unsigned long long)max_len);
-        }
+        if (lane == 0 && max_len) atomicMax(stats + 4, (unsigned long long)max_len);
     }
 }
 
@@ -515,20 +451,16 @@ __global__ void __launch_bounds__(RQ_BLOCK) rt_camera_rays_kernel(CameraRays src
 // ---- host side ----
 // One query workspace per device: the launch's ray counter and the stack
 // spill area (indexed by the resident grid's global thread id), so one query
-// kernel at a time may use it.  Launches are ordered on it by an event — each
-// waits on its stream for the previous launch, whatever stream that was on —
-// under the mutex until the launch is enqueued (as the megakernel's spill
-// area, path_kernel.hip).
+// kernel at a time may use it, in rt_workspace.h's order.  Its size depends
+// on the device alone: nothing is ever replaced.
 struct QueryWorkspace {
     uint2 *spill = nullptr;
     size_t spill_threads = 0;
     uint32_t *fetch = nullptr;
-    hipEvent_t last = nullptr;
-    bool recorded = false;
+    SerialEvent serial;
     int blocks = 0; // the resident grid: RQ_WAVES blocks per CU
 };
-std::mutex g_query_mu;
-std::map<int, QueryWorkspace> g_query;
+DeviceSlots<QueryWorkspace> g_query;
 
 // max(RT_STACK_DEPTH, RT_BVH_STACK) entries in all: the KD part needs <= RT_STACK_DEPTH, the BVH part <= RT_BVH_STACK
 constexpr int kSpillDepth = (RT_BVH_STACK > RT_STACK_DEPTH ? RT_BVH_STACK : RT_STACK_DEPTH) - RQ_LDS;
@@ -539,20 +471,21 @@ using QueryKernel = void (*)(RtDevScene, SRC, SINK, uint32_t, int, uint32_t *, u
 
 // The device's workspace, made on first use, with `stream` waiting for the
 // previous launch that used it and the ray counter zeroed on `stream`
-// (g_query_mu is held by the caller until query_launched); nullptr on error.
+// (g_query.mu is held by the caller until the launch is recorded); nullptr on error.
 QueryWorkspace *query_workspace(hipStream_t stream)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    QueryWorkspace &w = g_query[dev];
+    QueryWorkspace *slot = g_query.current();
+    if (!slot) return nullptr;
+    QueryWorkspace &w = *slot;
     if (!w.blocks) {
+        int dev = 0;
         hipDeviceProp_t prop;
-        const int cus = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0
+        const int cus = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
+                                prop.multiProcessorCount > 0
                             ? prop.multiProcessorCount
                             : 256;
         w.blocks = cus * RQ_WAVES;
     }
-    if (!w.last && hipEventCreateWithFlags(&w.last, hipEventDisableTiming) != hipSuccess) return nullptr;
     if (!w.fetch) {
         void *p = nullptr;
         if (hipMalloc(&p, 64) != hipSuccess) return nullptr;
@@ -565,7 +498,7 @@ QueryWorkspace *query_workspace(hipStream_t stream)
         w.spill = (uint2 *)p;
         w.spill_threads = threads;
     }
-    if (w.recorded && hipStreamWaitEvent(stream, w.last, 0) != hipSuccess) return nullptr;
+    if (!w.serial.wait_on(stream)) return nullptr;
     if (hipMemsetAsync(w.fetch, 0, sizeof(uint32_t), stream) != hipSuccess) return nullptr;
     return &w;
 }
@@ -578,13 +511,6 @@ int query_grid(const QueryWorkspace &w, long long n, int per_cu)
     return (int)(need < resident ? need : resident);
 }
 
-int query_launched(QueryWorkspace &w, hipStream_t stream)
-{
-    if (hipGetLastError() != hipSuccess || hipEventRecord(w.last, stream) != hipSuccess) return -1;
-    w.recorded = true;
-    return 0;
-}
-
 bool query_kd_only(const RtDevScene &sc, int traversal)
 {
     return traversal == RT_TRAVERSAL_KD || sc.bvh_nodes == nullptr || sc.bvh4 == nullptr;
@@ -594,12 +520,12 @@ template <typename SRC, typename SINK>
 int launch_query(QueryKernel<SRC, SINK> kernel, const RtDevScene &sc, const SRC &src, const SINK &sink, long long n, int traversal,
                  unsigned long long *stats, hipStream_t stream)
 {
-    std::lock_guard<std::mutex> g(g_query_mu);
+    std::lock_guard<std::mutex> g(g_query.mu);
     QueryWorkspace *w = query_workspace(stream);
     if (!w) return -1;
     hipLaunchKernelGGL(kernel, dim3(query_grid(*w, n, RQ_WAVES)), dim3(RQ_BLOCK), 0, stream, sc, src, sink, (uint32_t)n,
                        (int)query_kd_only(sc, traversal), w->fetch, stats, w->spill, (int)w->spill_threads);
-    return query_launched(*w, stream);
+    return w->serial.record(stream) ? 0 : -1;
 }
 
 CameraRays camera_source(const RtDevCamera &cam, int width, int height)
@@ -637,13 +563,13 @@ int rt_launch_trace_paths(const RtDevScene &sc, const float *rays, uint32_t *rng
 {
     static_assert(PQ_WAVES <= RQ_WAVES && PQ_LDS >= RQ_LDS, "rt_path_query_kernel within the shared spill area");
     const BufferRays src{reinterpret_cast<const float2 *>(rays)};
-    std::lock_guard<std::mutex> g(g_query_mu);
+    std::lock_guard<std::mutex> g(g_query.mu);
     QueryWorkspace *w = query_workspace(stream);
     if (!w) return -1;
     hipLaunchKernelGGL(rt_path_query_kernel, dim3(query_grid(*w, n, PQ_WAVES)), dim3(RQ_BLOCK), 0, stream, sc, src, rng,
                        radiance, sq, (uint32_t)n, samples, max_depth > 0 ? max_depth : RT_WATCHDOG_BOUNCES, accumulate,
                        (int)query_kd_only(sc, traversal), w->fetch, stats, w->spill, (int)w->spill_threads);
-    return query_launched(*w, stream);
+    return w->serial.record(stream) ? 0 : -1;
 }
 
 int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width, int height, float *depth,
@@ -665,16 +591,9 @@ int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *
 
 void rt_query_shutdown()
 {
-    std::lock_guard<std::mutex> g(g_query_mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto &kv : g_query) {
-        if (hipSetDevice(kv.first) != hipSuccess) continue;
-        if (kv.second.recorded) (void)hipEventSynchronize(kv.second.last);
-        if (kv.second.spill) (void)hipFree(kv.second.spill);
-        if (kv.second.fetch) (void)hipFree(kv.second.fetch);
-        if (kv.second.last) (void)hipEventDestroy(kv.second.last);
-    }
-    g_query.clear();
-    (void)hipSetDevice(cur);
+    g_query.shutdown([](QueryWorkspace &w) {
+        w.serial.destroy();
+        if (w.spill) (void)hipFree(w.spill);
+        if (w.fetch) (void)hipFree(w.fetch);
+    });
 }

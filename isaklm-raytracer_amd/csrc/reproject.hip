@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "reproject_math.h"
+#include "rt_launch.h"
 
 #define RP_TILE_W 32
 #define RP_TILE_H 8

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "bvh_trace.h"
+#include "path_event.h"
 #include "rt_kernels.h"
 #include "rt_launch.h"
 #include "wf_check_grid.h"

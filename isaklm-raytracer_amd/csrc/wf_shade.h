@@ -129,6 +129,10 @@ __device__ __forceinline__ void first_ray(const WfState &st, const RtDevFrame &f
 // queue iteration as the shadow ray (p.dual, p.ext_live).  The shadow result
 // is still applied first (L += direct * T, then T /= p), in the reference's
 // order.  Any shade_step (DUAL or not) resumes such a path correctly.
+//
+// The shadow result and the regeneration are path_event.h's; the bounce is
+// path_bounce's text, kept here because calling the helper changes the register
+// allocation of wf_shade and of every finisher (profiles/path_event).
 template <bool COUNT, bool DUAL = false, typename P>
 __device__ __forceinline__ bool shade_step(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera &cam,
                                            P &p, int hit, float bx, float by, float bz, int limit, Cnt &c)
@@ -182,13 +186,7 @@ __device__ __forceinline__ bool shade_step(const RtDevScene &sc, const RtDevFram
             }
         }
     } else {
-        Vec3D direct = rt_v3(0.0f, 0.0f, 0.0f);
-        if (hit >= 0 && hit == p.light)
-            direct = light_contribution(sc, p.light, bx, by, bz, p.ro, p.rd, p.rp, p.snorm);
-        if (COUNT && hit >= 0 && material_of(sc, hit).tex) c.v[RT_CNT_TEXEL] += 2; // every hit is shaded
-        p.L = p.L + direct * p.T;
-        p.rd = p.cont;
-        p.shadow = false;
+        path_shadow_result<COUNT>(sc, p, hit, bx, by, bz, c);
         if (p.dual) { // the roulette was drawn at the set-up
             p.dual = false;
             roulette = false;
@@ -231,12 +229,7 @@ __device__ __forceinline__ bool shade_step(const RtDevScene &sc, const RtDevFram
         if (p.passes_left > 0) {
             want = start_sample<COUNT>(fr, cam, (int)slot, p.passes_left, p.rng, fb, sq, count, p.ro, p.rd, c);
             if (want) {
-                p.T = rt_v3(1.0f, 1.0f, 1.0f);
-                p.L = rt_v3(0.0f, 0.0f, 0.0f);
-                p.inside = false;
-                p.prev_type = PRIMARY;
-                p.depth = 1;
-                p.shadow = false;
+                path_begin(p, 1);
             }
         }
     }

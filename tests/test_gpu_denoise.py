@@ -128,6 +128,35 @@ def test_stream_and_untouched_tail():
         assert _HIP.hipStreamDestroy(s) == 0
 
 
+def test_two_sizes_on_two_streams_equal_alone():
+    """two calls of different frame sizes on two streams, issued back to back with nothing between them: the
+    second replaces the device's workspace while the first may still be using it, so the library waits for the
+    first before it frees the buffers.  Each output is the one of the same call made alone."""
+    shapes = ((96, 64), (64, 48))
+    streams = [_stream(), _stream()]
+    frames = [denoise_ref.case(W, H, "defaults") for W, H in shapes]
+    gs = [_gbuffer(f) for f, _ in frames]
+    devs = [[Dev(f[k]) for k in ("depth", "normal", "albedo")] for f, _ in frames]
+    outs = [Dev(np.zeros(3 * W * H, F)) for W, H in shapes]
+    try:
+        for (W, H), g, (d_depth, d_normal, d_albedo), d_out, s in zip(shapes, gs, devs, outs, streams):
+            rt.denoise_device(g.g, (d_depth.p, d_normal.p, d_albedo.p), W, H, d_out.p, stream=s.value)
+        for s in streams:
+            assert _HIP.hipStreamSynchronize(s) == 0
+        got = [d.read() for d in outs]
+        alone = [rt.denoise(g, f) for g, (f, _) in zip(gs, frames)]
+    finally:
+        for d in outs + [d for ds in devs for d in ds]:
+            d.free()
+        for g in gs:
+            g.free()
+        for s in streams:
+            assert _HIP.hipStreamDestroy(s) == 0
+    for (W, H), out, one, (_, ref) in zip(shapes, got, alone, frames):
+        _assert_same_bits(out.reshape(H, W, 3), one, f"{W}x{H} on its stream vs alone")
+        _assert_same_bits(one, ref, f"{W}x{H} alone vs restatement")
+
+
 # ---------------------------------------------------------------- a real frame
 W_REAL, H_REAL, SPP, DEPTH = 96, 64, 4, 8
 # relMSE(denoised 4 spp) / relMSE(raw 4 spp) measured on the MI355X (DESIGN.md "Denoising"; renders are

@@ -441,6 +441,45 @@ def test_query_between_chained_renders():
         assert _HIP.hipStreamDestroy(s) == 0
 
 
+def test_two_queries_on_two_streams_equal_serial():
+    """rt_trace_rays on one stream and rt_occluded on another, issued back to
+    back with nothing between them, share the device's query workspace (ray
+    counter, stack spill area): the library orders them on it.  n is twice the
+    resident grid's threads (CUs x RQ_WAVES = 4 blocks x 256), so the first
+    launch still holds the workspace when the second is enqueued.  Both
+    results equal the same calls made one after the other on the null stream."""
+    c = case("cornell")
+    sa, sb = _stream(), _stream()
+    cus = ctypes.c_int(0)
+    assert _HIP.hipDeviceGetAttribute(ctypes.byref(cus), 63, 0) == 0  # hipDeviceAttributeMultiprocessorCount
+    n = 2 * cus.value * 4 * 256
+    assert n > 0
+    g = np.random.default_rng(21)
+    rays = np.concatenate([_inbox(g, c, n), _unit(g, n)], axis=1).astype(f32)
+    d_rays = Dev(rays)
+    outs = [Dev(_guarded(rt.RAY_HIT, n)) for _ in range(2)] + [Dev(_guarded(np.dtype(np.uint8), n)) for _ in range(2)]
+    (d_hits0, d_hits1, d_occ0, d_occ1) = outs
+    try:
+        rt.trace_rays_device(c.run.dev, d_rays.p, n, d_hits0.p)
+        rt.occluded_device(c.run.dev, d_rays.p, None, n, d_occ0.p)
+        rt.trace_rays_device(c.run.dev, d_rays.p, n, d_hits1.p, stream=sa.value)
+        rt.occluded_device(c.run.dev, d_rays.p, None, n, d_occ1.p, stream=sb.value)
+        assert _HIP.hipStreamSynchronize(sa) == 0 and _HIP.hipStreamSynchronize(sb) == 0
+        hits0, hits1, occ0, occ1 = (d.read() for d in outs)
+    finally:
+        for d in [d_rays] + outs:
+            d.free()
+        for s in (sa, sb):
+            assert _HIP.hipStreamDestroy(s) == 0
+    assert np.array_equal(hits1.view(np.uint8), hits0.view(np.uint8)), "rt_trace_rays on a stream vs serial"
+    assert np.array_equal(occ1, occ0), "rt_occluded on a stream vs serial"
+    assert (hits1[n:].view(np.uint8) == 0xCD).all() and (occ1[n:] == 0xCD).all(), "tail written"
+    # the inputs are not trivial, and a ray is occluded (tmax = +inf) exactly where it hits
+    hit = hits0["triangle"][:n] >= 0
+    assert 0.25 * n < hit.sum() < n
+    assert np.array_equal(occ0[:n], hit.astype(np.uint8))
+
+
 # ------------------------------------------------------------------ 8. torch
 def test_torch_tensors_on_the_current_stream():
     """rays in a torch device tensor, the query enqueued on torch's current
