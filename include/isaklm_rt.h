@@ -70,7 +70,9 @@ extern "C" {
  * new struct, nothing existing moved; RT_HAS_TRACE_PATHS is its compile-time
  * feature test.  Temporal reprojection (rt_reproject, rt_reproject_host,
  * rt_default_reproject_options, RtReprojectOptions) was added within version
- * 12 in the same way; RT_HAS_REPROJECT is its feature test.
+ * 12 in the same way; RT_HAS_REPROJECT is its feature test.  So were the
+ * path samplers (rt_sample_paths, rt_sampler_rays, rt_sampler_rays_host,
+ * RtSampler); RT_HAS_PATH_SAMPLERS is their feature test.
  * An integrator checks
  * rt_abi_version() == RT_ABI_VERSION at start-up: a binary built against an
  * older header would otherwise link (C linkage) and mis-pass arguments. */
@@ -763,6 +765,99 @@ typedef struct RtPathOptions {
 void rt_default_path_options(RtPathOptions *opt);
 int rt_trace_paths(rt_scene_t scene, const float *rays_device, uint32_t *rng_device, long long n,
                    float *radiance_device, float *sq_luminance_device, const RtPathOptions *opt);
+
+/* ---------------- radiance queries that make their own rays (within ABI 12, an addition) ----------------
+ * rt_trace_paths for rays the library draws itself, on the device, from each element's own RNG state: a second
+ * camera path beside rt_render (pinhole, equirectangular, fisheye, orthographic) and a probe / baking primitive
+ * (cosine-weighted hemispheres over surface points).  No ray buffer exists: a lane draws its element's next ray
+ * where it would otherwise re-read the caller's.
+ *
+ * A sampler maps (element e, RNG state st) to (origin o, direction d, new st).  Every operation is a correctly
+ * rounded float32 one (+ - * / sqrtf, compares) or the library's sincos (rt_libm.h), unfused, in the order written;
+ * draws are the renderer's get_random_unilateral, in the order written.  Element e of an image sampler is pixel
+ * (x, y) = (e % width, e / width), row 0 = bottom (the G_Buffer's orientation); W, H = (float)width, height; R is
+ * the camera's rotation (Camera::rotation(), a host-side frame constant) and R*v = (v.x*i + v.y*j) + v.z*k;
+ * TAU = PI * 2 with the reference's PI = 3.1415926536f.
+ *
+ *   RT_SAMPLER_PINHOLE (4 draws)  the renderer's camera sample (rt/path_tracing.cuh:381-391, :327-336): draws rx,
+ *       ry; dir = normalize(t*((float)x + rx - hw)/hw, t*((float)y + ry - hh)/hw, 1) with t = tanf(FOV / 2),
+ *       hw = (float)(width / 2), hh = (float)(height / 2) (integer halves; hw divides on both axes); d = R*dir;
+ *       theta = draw * TAU; r = sqrtf(draw) * aperture_radius; (s, c) = sincos(theta);
+ *       o = (position + R*(r*c, 0, 0)) + R*(0, r*s, 0).
+ *   RT_SAMPLER_EQUIRECT (2 draws: rx, ry)  lon = ((float)x + rx) / W * TAU - PI;
+ *       lat = ((float)y + ry) / H * PI - PI * 0.5f; (sl, cl) = sincos(lon); (sa, ca) = sincos(lat);
+ *       d = R*(ca*sl, sa, ca*cl); o = position.
+ *   RT_SAMPLER_FISHEYE (2 draws: rx, ry)  equidistant, the image circle inscribed in the shorter side:
+ *       rad = min(W, H) * 0.5f; u = (((float)x + rx) - W*0.5f) / rad; v = (((float)y + ry) - H*0.5f) / rad;
+ *       r = sqrtf(u*u + v*v); if !(r <= 1): d = 0 (outside the circle; the 2 draws are taken all the same); else
+ *       theta = r * (FOV * 0.5f); (s, c) = sincos(theta); k = r > 0 ? s / r : 0; d = R*(k*u, k*v, c).  o = position.
+ *   RT_SAMPLER_ORTHO (2 draws: rx, ry)  u = (((float)x + rx) - W*0.5f) / (W*0.5f) * ortho_half_width;
+ *       v = (((float)y + ry) - H*0.5f) / (W*0.5f) * ortho_half_width (square pixels);
+ *       o = (position + R*(u, 0, 0)) + R*(0, v, 0); d = R*(0, 0, 1).
+ *   RT_SAMPLER_HEMISPHERE (2 draws, diffuse_direction's order, rt/path_tracing.cuh:45-59)  element e reads 6 floats
+ *       of points_device: position p, normal n (used as given).  (ds, dc) = sincos(draw * TAU); ru2 = draw;
+ *       sq = sqrtf(ru2); d = sq*dc*t + sqrtf(1 - ru2)*n + sq*ds*b; o = p.  (t, b) is the branch-free frame of n
+ *       (Duff et al. 2017): sg = copysignf(1, n.z); a = -1 / (sg + n.z); q = n.x*n.y*a;
+ *       t = (1 + sg*n.x*n.x*a, sg*q, -sg*n.x); b = (q, sg + n.y*n.y*a, -n.y).  Cosine-weighted for a unit n: the
+ *       mean of L times pi is the irradiance at p.
+ *
+ * Pixel list (image kinds): with pixels_device, element i is the pixel pixels_device[i]; an index outside
+ * [0, width*height), compared unsigned, gives o = d = 0 and draws nothing — such a ray hits nothing: L = 0 and the
+ * RNG state stays.  Centre ray (image kinds; rt_sampler_rays with rng NULL): both jitter draws are taken as 0.5,
+ * there is no lens offset and nothing is drawn; for PINHOLE these are rt_camera_rays' rays bit for bit.
+ * NaN or infinite camera fields are safe (no float is converted to an int, nothing is indexed by one): such rays
+ * miss.
+ *
+ * THE CONTRACT.  rt_sample_paths with samples = k and accumulate = a gives the same radiance, sq_luminance and rng,
+ * bit for bit, as k rounds of { rt_sampler_rays; rt_trace_paths(samples = 1, accumulate = a || round > 1) }, in
+ * either traversal mode.  So a PINHOLE sampler with no pixel list run on a G_Buffer's random_numbers, frame_buffer,
+ * squared_luminance and sample_count with accumulate = 0 is rt_render(sample_count = 0, passes = k, adaptive = 0) on
+ * that G_Buffer, bit for bit in all four arrays — and a sampled image's outputs are a G_Buffer: rt_tonemap,
+ * rt_save_render and rt_gbuffer_save read it as it is.
+ *
+ * RT_E_INVALID before any GPU call: what rt_trace_paths checks; a null sampler or a kind out of range; image kinds
+ * with width or height < 1 or width*height > 2^31 - 1; no pixel list and n != width*height; FISHEYE with a FOV
+ * that is not finite or outside (0, 2 pi]; ORTHO with an ortho_half_width that is not finite or <= 0; HEMISPHERE
+ * with null or misaligned points; a misaligned pixels_device or sample_count_device; rt_sampler_rays(_host) with
+ * null rays, or with rng NULL for HEMISPHERE.  n == 0: RT_OK without a launch.  Nothing at index n or beyond is
+ * read or written.  Workspace, ordering and stats_device: rt_trace_paths' (no G_Buffer, chain or render workspace
+ * is touched).
+ *
+ * Not covered: AOVs and denoising for the non-pinhole models (rt_sampler_rays(rng = NULL) + rt_trace_rays gives
+ * a caller the centre hits), and adaptive sampling: every element takes every sample. */
+#define RT_HAS_PATH_SAMPLERS 1
+#define RT_SAMPLER_PINHOLE 0
+#define RT_SAMPLER_EQUIRECT 1
+#define RT_SAMPLER_FISHEYE 2
+#define RT_SAMPLER_ORTHO 3
+#define RT_SAMPLER_HEMISPHERE 4
+/* (with ISAKLM_RT_CALLER_TYPES the caller's Camera is not complete here: the field then is these 28 bytes, the
+ * layout ISAKLM_RT_CHECK_LAYOUT() asserts of Camera, and the caller copies its camera into them) */
+#ifdef ISAKLM_RT_CALLER_TYPES
+typedef struct RtSamplerCamera { float position[3]; float yaw, pitch, FOV, aperture_radius; } RtSamplerCamera;
+#else
+typedef Camera RtSamplerCamera;
+#endif
+typedef struct RtSampler {
+    int kind;                       /* RT_SAMPLER_* */
+    int width, height;              /* image kinds */
+    RtSamplerCamera camera;               /* image kinds: position, yaw, pitch; FOV: PINHOLE as the renderer, FISHEYE the full
+                                       angle across the image circle, (0, 2*pi]; aperture_radius: PINHOLE only */
+    float ortho_half_width;         /* ORTHO: world units from the centre to the left / right edge, finite, > 0 */
+    const int32_t *pixels_device;   /* image kinds, optional: n pixel indices; NULL: element i = pixel i and n == width*height */
+    const float *points_device;     /* HEMISPHERE: n x 6 floats (position, normal), 8-B aligned */
+} RtSampler;
+
+/* per element, `samples` times: (o, d, st) = sampler(e, st); (L, st) = trace_path(o, d, st); sums as rt_trace_paths.
+ * sample_count_device (optional, n ints): count = (accumulate ? count : 0) + samples. */
+int rt_sample_paths(rt_scene_t scene, const RtSampler *sampler, uint32_t *rng_device, long long n,
+                    float *radiance_device, float *sq_luminance_device, int *sample_count_device,
+                    const RtPathOptions *opt);
+/* one sample's rays, n x 6 floats, rt_trace_rays' layout; advances rng_device.  rng_device NULL: the centre rays
+ * (image kinds; RT_E_INVALID for HEMISPHERE). */
+int rt_sampler_rays(const RtSampler *sampler, uint32_t *rng_device, long long n, float *rays_device, void *stream);
+/* the same arithmetic on host arrays (pixels / points / rng / rays are host pointers), bit for bit */
+int rt_sampler_rays_host(const RtSampler *sampler, uint32_t *rng, long long n, float *rays);
 
 /* draw_frame's colour math (rt/render.cuh:37-59): correct_color(fb/count) ->
  * RGBA8 into a device buffer of width*height*4 bytes, row 0 = bottom. */

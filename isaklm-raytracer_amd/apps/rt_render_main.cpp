@@ -14,6 +14,16 @@
 //                  [--shard G N] [--device D] [--out PNG] [--quiet]
 //                  [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]
 //                  [--reproject-to "PX PY PZ YAW PITCH" [--spp2 N]]
+//                  [--camera-model pinhole|equirect|fisheye|ortho] [--ortho-half-width X]
+// --camera-model renders the frame through rt_sample_paths instead of
+// rt_render: each call draws --passes samples per pixel from the model's
+// sampler (RT_SAMPLER_*; fisheye reads the camera's FOV as the angle across the
+// image circle, ortho takes --ortho-half-width world units, default 2) into
+// the G_Buffer's four arrays, so --checkpoint, --resume and --out work
+// unchanged.  That path never runs the adaptive test and renders whole frames
+// of one camera: with an explicit --adaptive 1, --shard or --reproject-to the
+// flag is a usage error, and so is a model other than pinhole with --aov or
+// --denoise (those buffers are the pinhole camera's).
 // --reproject-to moves the camera after the --spp samples (FOV and aperture
 // stay): instead of the reference's reset the frame is carried over to the new
 // camera (rt_reproject, guided by rt_render_aov of both cameras) into a second
@@ -56,7 +66,8 @@ void usage()
             "                 [--passes P] [--adaptive 0|1] [--min-samples N] [--tolerance T] [--max-depth D]\n"
             "                 [--kernel mega|wavefront] [--shard G N] [--device D] [--out PNG] [--quiet]\n"
             "                 [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]\n"
-            "                 [--reproject-to \"PX PY PZ YAW PITCH\" [--spp2 N]]\n");
+            "                 [--reproject-to \"PX PY PZ YAW PITCH\" [--spp2 N]]\n"
+            "                 [--camera-model pinhole|equirect|fisheye|ortho] [--ortho-half-width X]\n");
 }
 
 // PFM: "PF" (3 channels) or "Pf" (1), width height, a negative scale = little-endian, rows bottom to top
@@ -153,8 +164,9 @@ int main(int argc, char **argv)
     int width = 1920, height = 1080, spp = 5000, passes = 64, adaptive = 1, min_samples = 100, max_depth = 0;
     int spp2 = 0;
     int device = 0, shard_id = 0, num_shards = 1, kernel = RT_KERNEL_WAVEFRONT;
-    float tolerance = 0.05f;
-    bool quiet = false, denoise = false;
+    int camera_model = -1; // RT_SAMPLER_*; -1: rt_render
+    float tolerance = 0.05f, ortho_half_width = 2.0f;
+    bool quiet = false, denoise = false, adaptive_given = false, shard_given = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&](void) -> const char * {
@@ -170,12 +182,12 @@ int main(int argc, char **argv)
         else if (a == "--height") height = atoi(next());
         else if (a == "--spp") spp = atoi(next());
         else if (a == "--passes") passes = atoi(next());
-        else if (a == "--adaptive") adaptive = atoi(next());
+        else if (a == "--adaptive") { adaptive = atoi(next()); adaptive_given = true; }
         else if (a == "--min-samples") min_samples = atoi(next());
         else if (a == "--tolerance") tolerance = (float)atof(next());
         else if (a == "--max-depth") max_depth = atoi(next());
         else if (a == "--kernel") kernel = std::string(next()) == "mega" ? RT_KERNEL_MEGA : RT_KERNEL_WAVEFRONT;
-        else if (a == "--shard") { shard_id = atoi(next()); num_shards = atoi(next()); }
+        else if (a == "--shard") { shard_id = atoi(next()); num_shards = atoi(next()); shard_given = true; }
         else if (a == "--device") device = atoi(next());
         else if (a == "--out") out = next();
         else if (a == "--quiet") quiet = true;
@@ -185,6 +197,12 @@ int main(int argc, char **argv)
         else if (a == "--denoise") denoise = true;
         else if (a == "--reproject-to") reproject_to = next();
         else if (a == "--spp2") spp2 = atoi(next());
+        else if (a == "--camera-model") {
+            const std::string m = next();
+            camera_model = m == "pinhole" ? RT_SAMPLER_PINHOLE : m == "equirect" ? RT_SAMPLER_EQUIRECT
+                           : m == "fisheye" ? RT_SAMPLER_FISHEYE : m == "ortho" ? RT_SAMPLER_ORTHO : -2;
+        }
+        else if (a == "--ortho-half-width") ortho_half_width = (float)atof(next());
         else {
             usage();
             return 2;
@@ -192,6 +210,13 @@ int main(int argc, char **argv)
     }
     if (scene_path.empty() == gen_name.empty() || width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || spp2 < 0 ||
         (spp2 > 0 && reproject_to.empty())) {
+        usage();
+        return 2;
+    }
+    // the sampled path: whole frames of one camera, every pixel every sample; first-hit buffers are the pinhole's
+    if (camera_model == -2 ||
+        (camera_model >= 0 && ((adaptive_given && adaptive != 0) || shard_given || !reproject_to.empty())) ||
+        (camera_model > RT_SAMPLER_PINHOLE && (!aov.empty() || denoise))) {
         usage();
         return 2;
     }
@@ -247,7 +272,18 @@ int main(int argc, char **argv)
     }
     while (sample_count < spp) {
         opt.passes = passes < spp - sample_count ? passes : spp - sample_count;
-        if (rt_render(prepared, g_buffer, camera, sample_count, &opt) != RT_OK) return fail("render");
+        if (camera_model >= 0) {
+            const RtSampler sampler = {camera_model, width, height, camera, ortho_half_width, nullptr, nullptr};
+            RtPathOptions po;
+            rt_default_path_options(&po);
+            po.samples = opt.passes;
+            po.max_depth = max_depth;
+            po.accumulate = sample_count > 0;
+            if (rt_sample_paths(prepared, &sampler, g_buffer.random_numbers, (long long)width * height,
+                                (float *)g_buffer.frame_buffer, g_buffer.squared_luminance, g_buffer.sample_count,
+                                &po) != RT_OK)
+                return fail("sample_paths");
+        } else if (rt_render(prepared, g_buffer, camera, sample_count, &opt) != RT_OK) return fail("render");
         sample_count += opt.passes;
         if (!checkpoint.empty() && rt_gbuffer_save(g_buffer, width, height, sample_count, checkpoint.c_str()) != RT_OK)
             return fail("checkpoint");

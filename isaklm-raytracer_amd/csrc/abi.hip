@@ -22,6 +22,7 @@
 #include "reproject_math.h"
 #include "rt_launch.h"
 #include "rt_workspace.h"
+#include "sampler_math.h"
 
 // host/reproject_host.cpp: the overlap rule
 bool rt_rp_frames_overlap(const void *src_fb, const void *src_sq, const void *src_count, const void *dst_fb,
@@ -986,6 +987,65 @@ int rt_trace_paths(rt_scene_t scene, const float *rays, uint32_t *rng, long long
                        rt_launch_trace_paths(scene->dev, rays, rng, n, radiance, sq_luminance, o.samples ? o.samples : 1,
                                              o.max_depth, o.accumulate, o.traversal, o.stats_device, stream),
                        stream);
+}
+
+// rt_trace_paths for rays a sampler draws on the device (sampler_math.h)
+int rt_sample_paths(rt_scene_t scene, const RtSampler *sampler, uint32_t *rng, long long n, float *radiance,
+                    float *sq_luminance, int *sample_count, const RtPathOptions *opt)
+{
+    RtPathOptions o;
+    if (opt) o = *opt; else rt_default_path_options(&o);
+    if (!scene) { rt_set_error("rt_sample_paths: null scene"); return RT_E_INVALID; }
+    if (!rng || !radiance) { rt_set_error("rt_sample_paths: null rng or radiance"); return RT_E_INVALID; }
+    if (!count_ok("rt_sample_paths", n)) return RT_E_INVALID;
+    if (misaligned(rng, 4) || misaligned(radiance, 4) || misaligned(sq_luminance, 4) || misaligned(sample_count, 4) ||
+        misaligned(o.stats_device, 8)) {
+        rt_set_error("rt_sample_paths: misaligned pointer (stats_device 8 B, rng, radiance, sq_luminance and "
+                     "sample_count 4 B)");
+        return RT_E_INVALID;
+    }
+    if (o.samples < 0 || o.samples > (1 << 20) || o.max_depth < 0 || o.max_depth > RT_WATCHDOG_BOUNCES ||
+        (o.accumulate != 0 && o.accumulate != 1)) {
+        rt_set_error("rt_sample_paths: samples %d (0 .. 2^20), max_depth %d (0 .. 2^24 - 1) or accumulate %d (0 / 1)",
+                     o.samples, o.max_depth, o.accumulate);
+        return RT_E_INVALID;
+    }
+    if (!traversal_ok("rt_sample_paths", o.traversal)) return RT_E_INVALID;
+    RtDevSampler smp;
+    if (const char *why = rt_sampler_resolve(sampler, n, &smp)) {
+        rt_set_error("rt_sample_paths: %s", why);
+        return RT_E_INVALID;
+    }
+    if (n == 0) return RT_OK;
+    if (!stack_depth_ok("rt_sample_paths", scene)) return RT_E_UNSUPPORTED;
+    rt_register_shutdown();
+    hipStream_t stream = (hipStream_t)o.stream;
+    return launch_done("rt_sample_paths",
+                       rt_launch_sample_paths(scene->dev, smp, rng, n, radiance, sq_luminance, sample_count,
+                                              o.samples ? o.samples : 1, o.max_depth, o.accumulate, o.traversal,
+                                              o.stats_device, stream),
+                       stream);
+}
+
+int rt_sampler_rays(const RtSampler *sampler, uint32_t *rng, long long n, float *rays, void *stream)
+{
+    if (!rays || misaligned(rays, 8) || misaligned(rng, 4)) {
+        rt_set_error("rt_sampler_rays: null or misaligned rays (8 B), or misaligned rng (4 B)");
+        return RT_E_INVALID;
+    }
+    if (!count_ok("rt_sampler_rays", n)) return RT_E_INVALID;
+    RtDevSampler smp;
+    if (const char *why = rt_sampler_resolve(sampler, n, &smp)) {
+        rt_set_error("rt_sampler_rays: %s", why);
+        return RT_E_INVALID;
+    }
+    if (!rng && smp.kind == RT_SAMPLER_HEMISPHERE) {
+        rt_set_error("rt_sampler_rays: a hemisphere sampler has no centre ray (null rng)");
+        return RT_E_INVALID;
+    }
+    if (n == 0) return RT_OK;
+    return launch_done("rt_sampler_rays", rt_launch_sampler_rays(smp, rng, n, rays, (hipStream_t)stream),
+                       (hipStream_t)stream);
 }
 
 // (min_width 2: the camera's half width divides; the denoiser has no camera and takes a 1-pixel column)

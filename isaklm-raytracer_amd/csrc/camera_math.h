@@ -21,6 +21,23 @@ inline RtDevCamera rt_device_camera(const Camera &cam)
     return dc;
 }
 
+// rt_device_camera for a camera that may hold any floats.  The library's trigonometry reduces its argument through
+// an int (rt_libm.h rt_reduce_pio2: angles of a few radians): a NaN, infinite or absurd angle never reaches it — such
+// a camera gets NaN constants, which fail every compare made on them.
+#define RT_CAMERA_MAX_ANGLE 524288.0f // 2^19
+inline RtDevCamera rt_device_camera_checked(const Camera &cam)
+{
+    if (fabsf(cam.yaw) <= RT_CAMERA_MAX_ANGLE && fabsf(cam.pitch) <= RT_CAMERA_MAX_ANGLE &&
+        fabsf(cam.FOV) <= RT_CAMERA_MAX_ANGLE)
+        return rt_device_camera(cam);
+    RtDevCamera dc;
+    for (int k = 0; k < 9; ++k) dc.R[k] = NAN;
+    dc.pos[0] = cam.position.x; dc.pos[1] = cam.position.y; dc.pos[2] = cam.position.z;
+    dc.tan_half_fov = NAN;
+    dc.aperture = cam.aperture_radius;
+    return dc;
+}
+
 RT_HD RtM3 rt_camera_rotation(const RtDevCamera &cam)
 {
     RtM3 m = {rt_v3(cam.R[0], cam.R[1], cam.R[2]), rt_v3(cam.R[3], cam.R[4], cam.R[5]),

@@ -1,6 +1,7 @@
 // query.hip — the batched ray query (rt_trace_rays), the occlusion query
-// (rt_occluded), the radiance query (rt_trace_paths), the camera-ray generator
-// (rt_camera_rays) and the first-hit AOV pass (rt_render_aov).
+// (rt_occluded), the radiance queries (rt_trace_paths, rt_sample_paths), the
+// ray generators (rt_camera_rays, rt_sampler_rays) and the first-hit AOV pass
+// (rt_render_aov).
 //
 // The closest-hit query is the renderer's own: trace_ray (rt/trace_ray.cuh:
 // 244-318) as rt_kernels.h trace() restates it, sped up by the conservative
@@ -14,6 +15,7 @@
 //   rt_occluded     rays + tmax from buffers -> one byte per ray
 // and a third that runs the renderer's whole path loop on the caller's rays:
 //   rt_trace_paths  rays + RNG states        -> summed radiance per ray
+//   rt_sample_paths a sampler + RNG states   -> summed radiance per element
 //
 // One ray per lane; the lanes of a wave take their next rays together from a
 // global counter (one wave-aggregated atomic per round).  The traversal stack
@@ -37,6 +39,7 @@
 #include "rt_kernels.h"
 #include "rt_launch.h"
 #include "rt_workspace.h"
+#include "sampler_math.h"
 
 #define RQ_BLOCK 256
 #ifndef RQ_LDS
@@ -70,6 +73,7 @@ __device__ __forceinline__ void camera_ray_centre(const RtDevCamera &cam, int ha
 
 // ---- ray sources ----
 struct BufferRays { // n x 6 floats (o.xyz d.xyz), 8-B aligned: three 8-B loads, 1,536 contiguous bytes per wave
+    static constexpr bool per_sample = false; // rt_path_query_kernel: loaded once per ray
     const float2 *rays;
     __device__ __forceinline__ void load(uint32_t e, Vec3D &o, Vec3D &d) const
     {
@@ -77,6 +81,19 @@ struct BufferRays { // n x 6 floats (o.xyz d.xyz), 8-B aligned: three 8-B loads,
         const float2 a = p[0], b = p[1], c = p[2];
         o = rt_v3(a.x, a.y, b.x);
         d = rt_v3(b.y, c.x, c.y);
+    }
+};
+struct SamplerRays { // sampler_math.h: element e's next ray, drawn from the element's own RNG state
+    static constexpr bool per_sample = true; // rt_path_query_kernel: drawn once per sample
+    RtDevSampler smp;
+    int *count; // sample_count_device (optional)
+    __device__ __forceinline__ void sample(uint32_t e, uint32_t &st, Vec3D &o, Vec3D &d) const
+    {
+        rt_sampler_ray<false>(smp, e, st, o, d);
+    }
+    __device__ __forceinline__ void done(uint32_t e, int samples, int accumulate) const
+    {
+        if (count) count[e] = (accumulate ? count[e] : 0) + samples;
     }
 };
 struct CameraRays { // ray e = the centre of pixel (e % width, e / width), row 0 = bottom
@@ -335,8 +352,15 @@ __global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
 // stats (optional) adds [0] rays, [1] paths, [2] trace_ray calls, [3] paths
 // cut at `limit`; [4] is the longest path (a maximum).  The per-lane counts
 // are 32-bit: a lane makes fewer than 2^32 queries in any launch that ends.
+//
+// SRC: BufferRays (rt_trace_paths) loads the caller's ray once and restarts
+// every sample from it; SamplerRays (rt_sample_paths) draws each sample's ray
+// from p.rng where that restart stands — in the iteration the lane's previous
+// path ended in, like any other regeneration — and keeps the element's
+// sample count.
+template <typename SRC>
 __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
-    rt_path_query_kernel(RtDevScene sc, BufferRays src, uint32_t *rng_io, float *radiance, float *sq_out, uint32_t n,
+    rt_path_query_kernel(RtDevScene sc, SRC src, uint32_t *rng_io, float *radiance, float *sq_out, uint32_t n,
                          int samples, int limit, int accumulate, int kd_only, uint32_t *fetch,
                          unsigned long long *stats, uint2 *spill, int spill_threads)
 {
@@ -367,12 +391,13 @@ __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
                     r[2] = sum.z;
                     if (sq_out) sq_out[e] = sum_sq;
                     rng_io[e] = p.rng;
+                    if constexpr (SRC::per_sample) src.done(e, samples, accumulate);
                     have_ray = false;
                 }
                 const uint32_t next = wave_next_index(fetch, lane); // for the lanes that are here
                 if (next >= n) break;
                 e = next;
-                src.load(e, o0, d0);
+                if constexpr (!SRC::per_sample) src.load(e, o0, d0);
                 p.rng = rng_io[e];
                 sum = rt_v3(0.0f, 0.0f, 0.0f);
                 sum_sq = 0.0f;
@@ -386,8 +411,12 @@ __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
                 ++n_rays;
             }
             --samples_left;
-            p.ro = o0;
-            p.rd = d0;
+            if constexpr (SRC::per_sample) {
+                src.sample(e, p.rng, p.ro, p.rd);
+            } else {
+                p.ro = o0;
+                p.rd = d0;
+            }
             path_begin(p, 0);
             have_path = true;
             ++n_paths;
@@ -433,6 +462,23 @@ __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
         }
         if (lane == 0 && max_len) atomicMax(stats + 4, (unsigned long long)max_len);
     }
+}
+
+// rt_sampler_rays: element e's next ray (CENTRE: its centre ray, no RNG), three 8-B stores per lane
+template <bool CENTRE>
+__global__ void __launch_bounds__(RQ_BLOCK) rt_sampler_rays_kernel(RtDevSampler smp, uint32_t *rng, float2 *rays, uint32_t n)
+{
+    const uint32_t e = blockIdx.x * RQ_BLOCK + threadIdx.x;
+    if (e >= n) return;
+    uint32_t st = 0;
+    if (!CENTRE) st = rng[e];
+    Vec3D o, d;
+    rt_sampler_ray<CENTRE>(smp, e, st, o, d);
+    if (!CENTRE) rng[e] = st;
+    float2 *p = rays + 3 * (size_t)e;
+    p[0] = make_float2(o.x, o.y);
+    p[1] = make_float2(o.z, d.x);
+    p[2] = make_float2(d.y, d.z);
 }
 
 // rt_camera_rays: ray y*W + x = the centre of pixel (x, y), three 8-B stores per lane
@@ -557,19 +603,49 @@ int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tma
     return launch_query(rt_occluded_kernel<BufferRaysTmax, ByteSink>, sc, src, sink, n, traversal, stats, stream);
 }
 
+namespace {
+template <typename SRC>
+int launch_path_query(const RtDevScene &sc, const SRC &src, uint32_t *rng, long long n, float *radiance, float *sq,
+                      int samples, int max_depth, int accumulate, int traversal, unsigned long long *stats,
+                      hipStream_t stream)
+{
+    static_assert(PQ_WAVES <= RQ_WAVES && PQ_LDS >= RQ_LDS, "rt_path_query_kernel within the shared spill area");
+    std::lock_guard<std::mutex> g(g_query.mu);
+    QueryWorkspace *w = query_workspace(stream);
+    if (!w) return -1;
+    hipLaunchKernelGGL(rt_path_query_kernel<SRC>, dim3(query_grid(*w, n, PQ_WAVES)), dim3(RQ_BLOCK), 0, stream, sc, src, rng,
+                       radiance, sq, (uint32_t)n, samples, max_depth > 0 ? max_depth : RT_WATCHDOG_BOUNCES, accumulate,
+                       (int)query_kd_only(sc, traversal), w->fetch, stats, w->spill, (int)w->spill_threads);
+    return w->serial.record(stream) ? 0 : -1;
+}
+} // namespace
+
 int rt_launch_trace_paths(const RtDevScene &sc, const float *rays, uint32_t *rng, long long n, float *radiance, float *sq,
                           int samples, int max_depth, int accumulate, int traversal, unsigned long long *stats,
                           hipStream_t stream)
 {
-    static_assert(PQ_WAVES <= RQ_WAVES && PQ_LDS >= RQ_LDS, "rt_path_query_kernel within the shared spill area");
-    const BufferRays src{reinterpret_cast<const float2 *>(rays)};
-    std::lock_guard<std::mutex> g(g_query.mu);
-    QueryWorkspace *w = query_workspace(stream);
-    if (!w) return -1;
-    hipLaunchKernelGGL(rt_path_query_kernel, dim3(query_grid(*w, n, PQ_WAVES)), dim3(RQ_BLOCK), 0, stream, sc, src, rng,
-                       radiance, sq, (uint32_t)n, samples, max_depth > 0 ? max_depth : RT_WATCHDOG_BOUNCES, accumulate,
-                       (int)query_kd_only(sc, traversal), w->fetch, stats, w->spill, (int)w->spill_threads);
-    return w->serial.record(stream) ? 0 : -1;
+    return launch_path_query(sc, BufferRays{reinterpret_cast<const float2 *>(rays)}, rng, n, radiance, sq, samples,
+                             max_depth, accumulate, traversal, stats, stream);
+}
+
+int rt_launch_sample_paths(const RtDevScene &sc, const RtDevSampler &smp, uint32_t *rng, long long n, float *radiance,
+                           float *sq, int *count, int samples, int max_depth, int accumulate, int traversal,
+                           unsigned long long *stats, hipStream_t stream)
+{
+    return launch_path_query(sc, SamplerRays{smp, count}, rng, n, radiance, sq, samples, max_depth, accumulate,
+                             traversal, stats, stream);
+}
+
+int rt_launch_sampler_rays(const RtDevSampler &smp, uint32_t *rng, long long n, float *rays, hipStream_t stream)
+{
+    const dim3 grid((uint32_t)((n + RQ_BLOCK - 1) / RQ_BLOCK)), block(RQ_BLOCK);
+    if (rng)
+        hipLaunchKernelGGL(rt_sampler_rays_kernel<false>, grid, block, 0, stream, smp, rng,
+                           reinterpret_cast<float2 *>(rays), (uint32_t)n);
+    else
+        hipLaunchKernelGGL(rt_sampler_rays_kernel<true>, grid, block, 0, stream, smp, rng,
+                           reinterpret_cast<float2 *>(rays), (uint32_t)n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width, int height, float *depth,

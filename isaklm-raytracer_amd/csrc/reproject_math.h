@@ -47,21 +47,9 @@ inline bool rt_rp_resolve(const RtReprojectOptions *opt, RtRpParams *p)
     return true;
 }
 
-// A camera's frame constants (host only).  The library's trigonometry reduces its argument through an int
-// (rt_libm.h rt_reduce_pio2: angles of a few radians): a NaN, infinite or absurd angle never reaches it — such a
-// camera gets NaN constants, which fail every compare of the projection, so every pixel resets.
-#define RT_RP_MAX_ANGLE 524288.0f // 2^19
-inline RtDevCamera rt_rp_camera(const Camera &cam)
-{
-    if (fabsf(cam.yaw) <= RT_RP_MAX_ANGLE && fabsf(cam.pitch) <= RT_RP_MAX_ANGLE && fabsf(cam.FOV) <= RT_RP_MAX_ANGLE)
-        return rt_device_camera(cam);
-    RtDevCamera dc;
-    for (int k = 0; k < 9; ++k) dc.R[k] = NAN;
-    dc.pos[0] = cam.position.x; dc.pos[1] = cam.position.y; dc.pos[2] = cam.position.z;
-    dc.tan_half_fov = NAN;
-    dc.aperture = cam.aperture_radius;
-    return dc;
-}
+// A camera's frame constants (host only): a NaN, infinite or absurd angle gives NaN constants (camera_math.h),
+// which fail every compare of the projection, so every pixel resets.
+inline RtDevCamera rt_rp_camera(const Camera &cam) { return rt_device_camera_checked(cam); }
 
 // one frame's arrays: the sums (NULL on the new camera's side) and the guides
 struct RtRpFrame {

@@ -10,6 +10,7 @@
 
 #include "rt_device.h"
 #include "rt_vecmath.h"
+#include "sampler_math.h"
 
 namespace rtk {
 
@@ -56,14 +57,8 @@ __device__ __forceinline__ bool rt_row_owned(const RtDevFrame &fr, int y)
 }
 
 // get_random_unilateral (rt/path_tracing.cuh:34-43)
-__device__ __forceinline__ float rng_next(uint32_t &st)
-{
-    uint32_t state = st * 747796405u + 2891336453u;
-    uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
-    uint32_t r = (word >> 22u) ^ word;
-    st = r;
-    return (float)r / (float)UINT32_MAX;
-}
+// (sampler_math.h rt_rng_next: one definition for the device and the host)
+__device__ __forceinline__ float rng_next(uint32_t &st) { return rt_rng_next(st); }
 
 __device__ __forceinline__ Vec3D ld3(const RtF4 &f) { return rt_v3(f.x, f.y, f.z); }
 

@@ -9,6 +9,7 @@
 struct RtDnParams; // denoise_math.h
 struct RtRpFrame;  // reproject_math.h
 struct RtRpParams;
+struct RtDevSampler; // sampler_math.h
 
 // path_kernel.hip: the megakernel and rt_tonemap
 int rt_launch_path(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera &cam, int stack_depth,
@@ -36,6 +37,10 @@ int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tma
 int rt_launch_trace_paths(const RtDevScene &sc, const float *rays, uint32_t *rng, long long n, float *radiance, float *sq,
                           int samples, int max_depth, int accumulate, int traversal, unsigned long long *stats,
                           hipStream_t stream);
+int rt_launch_sample_paths(const RtDevScene &sc, const RtDevSampler &smp, uint32_t *rng, long long n, float *radiance,
+                           float *sq, int *count, int samples, int max_depth, int accumulate, int traversal,
+                           unsigned long long *stats, hipStream_t stream);
+int rt_launch_sampler_rays(const RtDevSampler &smp, uint32_t *rng, long long n, float *rays, hipStream_t stream);
 void rt_query_shutdown();
 
 // denoise.hip

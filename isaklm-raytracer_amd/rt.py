@@ -76,6 +76,12 @@ class RtPathOptions(ctypes.Structure):
                 ("traversal", ctypes.c_int), ("stream", ctypes.c_void_p), ("stats_device", ctypes.c_void_p)]
 
 
+class RtSampler(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("camera", Camera),
+                ("ortho_half_width", ctypes.c_float), ("pixels_device", ctypes.c_void_p),
+                ("points_device", ctypes.c_void_p)]
+
+
 class RtAovBuffers(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
                 ("triangle", ctypes.c_void_p)]
@@ -251,6 +257,11 @@ def lib():
         L.rt_default_path_options.restype = None
         L.rt_trace_paths.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.POINTER(RtPathOptions)]
         L.rt_camera_rays.argtypes = [Camera, i, i, vp, vp]
+        if hasattr(L, "rt_sample_paths"):  # (added within ABI 12: an earlier ABI-12 library lacks it)
+            L.rt_sample_paths.argtypes = [vp, ctypes.POINTER(RtSampler), vp, ctypes.c_longlong, vp, vp, vp,
+                                          ctypes.POINTER(RtPathOptions)]
+            L.rt_sampler_rays.argtypes = [ctypes.POINTER(RtSampler), vp, ctypes.c_longlong, vp, vp]
+            L.rt_sampler_rays_host.argtypes = [ctypes.POINTER(RtSampler), vp, ctypes.c_longlong, vp]
         L.rt_render_aov.argtypes = [vp, Camera, i, i, ctypes.POINTER(RtAovBuffers), ctypes.POINTER(RtQueryOptions)]
         L.rt_default_denoise_options.argtypes = [ctypes.POINTER(RtDenoiseOptions)]
         L.rt_default_denoise_options.restype = None
@@ -700,6 +711,179 @@ def trace_paths(dscene, rays, rng, samples=1, max_depth=0, traversal=None, strea
             check(L.rt_download(_ptr(st), d_st, st.nbytes))
     out = (rad, sqv, rng)
     return out + (dict(zip(PATH_STATS, (int(v) for v in st))),) if stats else out
+
+
+# ---------------------------------------------------------------- path samplers
+SAMPLER_PINHOLE, SAMPLER_EQUIRECT, SAMPLER_FISHEYE, SAMPLER_ORTHO, SAMPLER_HEMISPHERE = range(5)
+SAMPLER_KINDS = {"pinhole": SAMPLER_PINHOLE, "equirect": SAMPLER_EQUIRECT, "fisheye": SAMPLER_FISHEYE,
+                 "ortho": SAMPLER_ORTHO, "hemisphere": SAMPLER_HEMISPHERE}
+
+
+class Sampler:
+    """RtSampler: how rt_sample_paths / rt_sampler_rays draw each element's rays (include/isaklm_rt.h has the
+    definition of every kind).  kind: a SAMPLER_* value or its name.  Image kinds take width, height and a Camera
+    (FISHEYE: camera.FOV is the full angle across the image circle; ORTHO: ortho_half_width), and optionally
+    `pixels`, an int32 array of pixel indices y * width + x (out-of-range entries give rays that hit nothing);
+    HEMISPHERE takes `points`, an (n, 6) float32 array of positions and normals."""
+
+    def __init__(self, kind, width=0, height=0, camera=None, ortho_half_width=0.0, pixels=None, points=None):
+        self.kind = SAMPLER_KINDS[kind] if isinstance(kind, str) else int(kind)
+        self.width, self.height = int(width), int(height)
+        self.camera = camera if camera is not None else Camera()
+        self.ortho_half_width = float(ortho_half_width)
+        self.pixels = None if pixels is None else np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+        self.points = None
+        if points is not None:
+            self.points = np.ascontiguousarray(points, dtype=np.float32)
+            if self.points.ndim != 2 or self.points.shape[1] != 6:
+                raise ValueError("points must have shape (n, 6)")
+
+    @property
+    def n(self):
+        """the number of elements: the points, the listed pixels, or the whole frame"""
+        if self.kind == SAMPLER_HEMISPHERE:
+            return 0 if self.points is None else len(self.points)
+        return self.width * self.height if self.pixels is None else len(self.pixels)
+
+    def struct(self, pixels_ptr=None, points_ptr=None):
+        """the RtSampler with the given pointers to its pixel list / points (device or host, as the call wants)"""
+        return RtSampler(self.kind, self.width, self.height, self.camera, self.ortho_half_width, _int_ptr(pixels_ptr),
+                         _int_ptr(points_ptr))
+
+
+def sample_paths_device(dscene, sampler, rng_ptr, n, radiance_ptr, sq_ptr=None, count_ptr=None, samples=1, max_depth=0,
+                        accumulate=False, traversal=None, stream=None, stats_ptr=None, pixels_ptr=None,
+                        points_ptr=None):
+    """rt_sample_paths on device memory: `sampler` a Sampler (its arrays are not used: pixels_ptr / points_ptr
+    are the device pointers to them); integer device pointers to n uint32 RNG states (read and written), n x 3
+    float32 radiance sums, optionally n float32 sums of squared luminance and n int32 sample counts — a
+    G_Buffer's four arrays, for a whole frame; stream: an integer hipStream_t — the call is then only enqueued."""
+    o = path_options(samples, max_depth, accumulate, traversal, stream, _int_ptr(stats_ptr))
+    smp = sampler.struct(pixels_ptr, points_ptr)
+    check(lib().rt_sample_paths(dscene.prepared, ctypes.byref(smp), _int_ptr(rng_ptr), int(n), _int_ptr(radiance_ptr),
+                                _int_ptr(sq_ptr), _int_ptr(count_ptr), ctypes.byref(o)))
+
+
+class _SamplerArrays:
+    """a Sampler's pixel list and points on the device for the length of a call"""
+
+    def __init__(self, sampler):
+        self.sampler = sampler
+        self.arrays = [a if a is not None and a.nbytes else None for a in (sampler.pixels, sampler.points)]
+        self.ctx = [_DeviceBytes(a.nbytes) if a is not None else None for a in self.arrays]
+
+    def __enter__(self):
+        ptrs = []
+        for a, c in zip(self.arrays, self.ctx):
+            ptrs.append(c.__enter__() if c else None)
+            if c:
+                check(lib().rt_upload(ptrs[-1], _ptr(a), a.nbytes))
+        # (an empty list still is a list: n == 0 is answered before the pointer is looked at)
+        if self.sampler.pixels is not None and ptrs[0] is None:
+            ptrs[0] = 4
+        if self.sampler.points is not None and ptrs[1] is None:
+            ptrs[1] = 8
+        return ptrs
+
+    def __exit__(self, *exc):
+        for c in self.ctx:
+            if c:
+                c.__exit__(*exc)
+        return False
+
+
+def sample_paths(dscene, sampler, rng, samples=1, max_depth=0, traversal=None, stream=None, stats=False,
+                 radiance=None, sq=None, count=None):
+    """Path-traced radiance of `samples` rays per element drawn by `sampler` (a Sampler) on the device from the
+    (n,) uint32 RNG states `rng`.  Returns (radiance (n, 3) float32, sq (n,) float32, rng_out (n,) uint32): the
+    SUMS over the samples, as trace_paths; with count=True also the (n,) int32 sample counts; with stats=True
+    also a dict of the call's counts (PATH_STATS).  Passing `radiance` (with `sq`, and `count` as an int32 array)
+    of an earlier call accumulates onto them (they are not modified)."""
+    n = sampler.n
+    rng = np.asarray(rng)
+    if rng.dtype != np.uint32 or rng.shape != (n,):
+        raise ValueError("rng must be a uint32 array of shape (n,)")
+    if radiance is None and sq is not None:
+        raise ValueError("sq without radiance: pass both arrays of the earlier call to accumulate")
+    want_count = count is not None and count is not False
+    count_arr = None if count is None or isinstance(count, bool) else np.asarray(count)
+    if count_arr is not None and radiance is None:
+        raise ValueError("count array without radiance: pass the arrays of the earlier call to accumulate")
+    for name, a, shape, dt in (("radiance", radiance, (n, 3), np.float32), ("sq", sq, (n,), np.float32),
+                               ("count", count_arr, (n,), np.int32)):
+        if a is not None and (np.asarray(a).dtype != dt or np.asarray(a).shape != shape):
+            raise ValueError(f"{name} must be a {np.dtype(dt).name} array of shape {shape}")
+    accumulate = radiance is not None
+    rng = np.ascontiguousarray(rng).copy()
+    rad = np.ascontiguousarray(radiance).copy() if accumulate else np.zeros((n, 3), np.float32)
+    sqv = np.ascontiguousarray(sq).copy() if sq is not None else np.zeros(n, np.float32)
+    cnt = np.ascontiguousarray(count_arr).copy() if count_arr is not None else np.zeros(n, np.int32)
+    L = lib()
+    st = np.zeros(5, dtype=np.uint64)
+    with _SamplerArrays(sampler) as (d_pix, d_pts), _DeviceBytes(rng.nbytes) as d_rng, \
+            _DeviceBytes(rad.nbytes) as d_rad, _DeviceBytes(sqv.nbytes) as d_sq, _DeviceBytes(cnt.nbytes) as d_cnt, \
+            _DeviceBytes(st.nbytes) as d_st:
+        if n:
+            check(L.rt_upload(d_rng, _ptr(rng), rng.nbytes))
+            if accumulate:
+                check(L.rt_upload(d_rad, _ptr(rad), rad.nbytes))
+                check(L.rt_upload(d_sq, _ptr(sqv), sqv.nbytes))
+                check(L.rt_upload(d_cnt, _ptr(cnt), cnt.nbytes))
+        if stats:
+            check(L.rt_memset(d_st, 0, st.nbytes))
+        sample_paths_device(dscene, sampler, d_rng, n, d_rad, d_sq, d_cnt if want_count else None, samples, max_depth,
+                            accumulate, traversal, stream, d_st if stats else None, d_pix, d_pts)
+        _synchronize_stream(stream)
+        if n:
+            check(L.rt_download(_ptr(rad), d_rad, rad.nbytes))
+            check(L.rt_download(_ptr(sqv), d_sq, sqv.nbytes))
+            check(L.rt_download(_ptr(rng), d_rng, rng.nbytes))
+            if want_count:
+                check(L.rt_download(_ptr(cnt), d_cnt, cnt.nbytes))
+        if stats:
+            check(L.rt_download(_ptr(st), d_st, st.nbytes))
+    out = (rad, sqv, rng) + ((cnt,) if want_count else ())
+    return out + (dict(zip(PATH_STATS, (int(v) for v in st))),) if stats else out
+
+
+def _sampler_rng(sampler, rng):
+    n = sampler.n
+    if rng is None:
+        return n, None
+    rng = np.asarray(rng)
+    if rng.dtype != np.uint32 or rng.shape != (n,):
+        raise ValueError("rng must be a uint32 array of shape (n,)")
+    return n, np.ascontiguousarray(rng).copy()
+
+
+def sampler_rays(sampler, rng=None):
+    """rt_sampler_rays: one sample's rays of every element of `sampler`, drawn on the device from the (n,) uint32
+    RNG states `rng`: (rays (n, 6) float32, rng_out).  rng None: the centre rays (image kinds), rays alone."""
+    n, rng = _sampler_rng(sampler, rng)
+    rays = np.zeros((n, 6), dtype=np.float32)
+    L = lib()
+    with _SamplerArrays(sampler) as (d_pix, d_pts), _DeviceBytes(4 * n) as d_rng, _DeviceBytes(rays.nbytes) as d_rays:
+        if n and rng is not None:
+            check(L.rt_upload(d_rng, _ptr(rng), rng.nbytes))
+        smp = sampler.struct(d_pix, d_pts)
+        check(L.rt_sampler_rays(ctypes.byref(smp), d_rng if rng is not None else None, n, d_rays, None))
+        if n:
+            check(L.rt_download(_ptr(rays), d_rays, rays.nbytes))
+            if rng is not None:
+                check(L.rt_download(_ptr(rng), d_rng, rng.nbytes))
+    return rays if rng is None else (rays, rng)
+
+
+def sampler_rays_host(sampler, rng=None):
+    """rt_sampler_rays_host: sampler_rays computed on the host, bit for bit (no GPU is touched)."""
+    n, rng = _sampler_rng(sampler, rng)
+    rays = np.zeros((max(n, 1), 6), dtype=np.float32)
+    pix, pts = sampler.pixels, sampler.points
+    smp = sampler.struct(None if pix is None else (pix.ctypes.data if len(pix) else 4),
+                         None if pts is None else (pts.ctypes.data if len(pts) else 8))
+    check(lib().rt_sampler_rays_host(ctypes.byref(smp), _ptr(rng) if rng is not None else None, n, _ptr(rays)))
+    rays = rays[:n]
+    return rays if rng is None else (rays, rng)
 
 
 def camera_rays(camera, width, height):
