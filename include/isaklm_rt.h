@@ -35,7 +35,8 @@
  * read each iteration's live path count).  Consecutive calls may use
  * different streams: a call waits for the previous calls' device work first
  * (they share the per-device workspace) — except a chained call
- * (RtOptions.overlap), see there.
+ * (RtOptions.overlap), see there.  Calls on one device from several host
+ * threads are serialised by the library.
  */
 #ifndef ISAKLM_RT_H
 #define ISAKLM_RT_H

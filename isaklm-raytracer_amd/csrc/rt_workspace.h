@@ -1,8 +1,8 @@
 // rt_workspace.h — one workspace per device, its users ordered by an event
 // (host only): the megakernel's spill area (path_kernel.hip), the query
-// workspace (query.hip), the denoiser's buffers (denoise.hip) and the
-// deviation block (abi.hip; no event, nothing in it is replaced).
-// wavefront.hip keeps its own Workspace.
+// workspace (query.hip), the denoiser's buffers (denoise.hip), the wavefront
+// workspace (wavefront.hip; several events, one per stream that may run last)
+// and the deviation block (abi.hip; no event, nothing in it is replaced).
 //
 // The order every user follows, under the table's mutex until its launch is
 // enqueued: (1) a buffer of the wrong size is replaced only after
@@ -19,14 +19,17 @@ struct SerialEvent {
     hipEvent_t ev = nullptr; // after the last launch that used the workspace
     bool recorded = false;
 
+    // the event ahead of its first use (wait_on makes it otherwise)
+    bool create() { return ev || hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess; }
     // `stream` waits for the previous user, whatever stream that was on
     bool wait_on(hipStream_t stream)
     {
-        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return false;
-        return !recorded || hipStreamWaitEvent(stream, ev, 0) == hipSuccess;
+        return create() && (!recorded || hipStreamWaitEvent(stream, ev, 0) == hipSuccess);
     }
     // the host waits for the previous user: before a buffer is freed or replaced
     bool wait_host() { return !recorded || hipEventSynchronize(ev) == hipSuccess; }
+    // the previous user's state, without waiting: hipSuccess (done, or there was none), hipErrorNotReady, or its failure
+    hipError_t query() { return recorded ? hipEventQuery(ev) : hipSuccess; }
     // after this user's launches on `stream` (false: one of them failed, or the record did)
     bool record(hipStream_t stream)
     {
@@ -44,7 +47,7 @@ struct SerialEvent {
 
 template <typename R>
 struct DeviceSlots {
-    std::mutex mu; // held by the caller from current() until its launch is enqueued
+    std::mutex mu; // held by the caller from current() / find() until its launch is enqueued
     std::map<int, R> slots;
 
     // the current device's slot, default-constructed on first use (nullptr: no current device)
@@ -52,6 +55,14 @@ struct DeviceSlots {
     {
         int dev = 0;
         return hipGetDevice(&dev) == hipSuccess ? &slots[dev] : nullptr;
+    }
+    // the current device's slot if it has one (nullptr: none yet, and none is made)
+    R *find()
+    {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+        auto it = slots.find(dev);
+        return it == slots.end() ? nullptr : &it->second;
     }
     // release(slot) for every device's slot with that device current; the
     // table is empty afterwards and the caller's device current again

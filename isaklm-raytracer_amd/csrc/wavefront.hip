@@ -36,6 +36,7 @@
 #include "path_event.h"
 #include "rt_kernels.h"
 #include "rt_launch.h"
+#include "rt_workspace.h"
 #include "wf_check_grid.h"
 
 using namespace rtk;
@@ -70,11 +71,9 @@ struct Pipe {
     hipStream_t stream = nullptr;
     uint32_t *host_count = nullptr;
     hipEvent_t ev[6] = {};   // RtOptions.profile
-    hipEvent_t join = nullptr;
+    SerialEvent join;      // after the pipeline's last launch
+    SerialEvent long_done; // whole-call mode: after a persistent wf_long on this stream
     hipEvent_t fin_done = nullptr; // after the finisher (the host polls it while kicking wf_long slices)
-    hipEvent_t long_done = nullptr; // whole-call mode: after a persistent wf_long on this stream
-    bool joined = false; // join recorded by a previous call
-    bool long_rec = false; // long_done recorded by a previous call
     RtProfile prof{};
 };
 
@@ -155,8 +154,7 @@ struct Workspace {
     Pipe pipe[WF_MAX_PIPES];
     bool streams_ok = false;
     hipEvent_t fork = nullptr, ev0 = nullptr, ev1 = nullptr, fin_ready = nullptr;
-    hipEvent_t long_ev = nullptr; // after the last wf_long slice on the caller's stream (queue mode)
-    bool recorded = false;   // long_ev recorded by a previous call
+    SerialEvent long_ev; // after the last wf_long slice on the caller's stream (queue mode)
     uint32_t *fin_live = nullptr; // 8 producer words (whole-call mode, one per call in flight: call % 8)
     uint32_t *heavy_list = nullptr; // (WfState.heavy_list: every pixel at most once)
     RtF4 *chk = nullptr;          // the exactness guard's records (2 x chk_cap x 3 RtF4; allocated on the
@@ -169,16 +167,14 @@ struct Workspace {
     uint32_t *verify_res = nullptr;
     bool verify_pending = false;
     bool verify_unread = false;
-    // after the last wf_verify (on whatever stream joined): every later launch on the workspace,
+    // after the last wf_verify (on whatever stream ran the join): every later launch on the workspace,
     // and the host's read of verify_res, wait for it — it rewrites every pixel's ownership word
-    hipEvent_t verify_ev = nullptr;
-    bool verify_rec = false;
+    SerialEvent verify_ev;
     int cus = 0;                                // compute units of the device (the finisher's grid)
     unsigned long long *long_log_buf = nullptr; // RT_DEBUG_LONG_LOG records
     // the guard's wf_check per record parity on pipeline 2: the event after it (the call two
     // later, whose finisher writes the same records, waits for it)
-    hipEvent_t chk_done[2] = {};
-    bool chk_rec[2] = {false, false};
+    SerialEvent chk_done[2];
     // RtOptions.profile of whole calls: per profiled call its finisher's span on the device
     // ({first wave start, last wave end}, s_memrealtime) in a ring of WF_PROF_SLOTS, resolved
     // into RtProfile records by rt_last_profile / rt_profile_history (they join first)
@@ -198,15 +194,22 @@ struct Workspace {
     RtProfile prof{};        // last profiled call
 };
 
-std::mutex g_ws_mu;
-std::map<int, Workspace *> g_ws; // per device (owned; released by rt_shutdown)
+// Per device (rt_workspace.h).  Every entry point of this file — rt_launch_wavefront, rt_wavefront_join,
+// rt_wavefront_device_init, rt_last_profile, rt_profile_history, rt_wavefront_shutdown — takes g_ws.mu once,
+// at its top, and holds it until its launches are enqueued (a queue-mode call: until launch_queue returns);
+// everything below them takes a Workspace & and never locks, launch_queue's pipeline threads included.
+DeviceSlots<Workspace> g_ws;
 
-Workspace &workspace(int dev)
+// What a join waits for, f(event) for each until one fails: the last hand-off check first (another stream
+// may have run it, and it rewrites every ownership word), every pipeline's last launch and persistent
+// wf_long, the queue mode's last wf_long slice
+template <typename F>
+bool each_tail(Workspace &w, F f)
 {
-    std::lock_guard<std::mutex> g(g_ws_mu);
-    Workspace *&w = g_ws[dev];
-    if (!w) w = new Workspace();
-    return *w;
+    if (!f(w.verify_ev)) return false;
+    for (Pipe &p : w.pipe)
+        if (!f(p.join) || !f(p.long_done)) return false;
+    return f(w.long_ev);
 }
 
 __global__ void wf_bind_stream() {}
@@ -220,13 +223,13 @@ int ensure_streams(Workspace &w, int npipes)
     if (!w.streams_ok) {
         if (hipEventCreateWithFlags(&w.fork, hipEventDisableTiming) != hipSuccess) return -1;
         if (hipEventCreateWithFlags(&w.fin_ready, hipEventDisableTiming) != hipSuccess) return -1;
-        if (hipEventCreateWithFlags(&w.long_ev, hipEventDisableTiming) != hipSuccess) return -1;
+        if (!w.long_ev.create()) return -1;
         if (hipEventCreate(&w.ev0) != hipSuccess || hipEventCreate(&w.ev1) != hipSuccess) return -1;
-        if (hipEventCreateWithFlags(&w.verify_ev, hipEventDisableTiming) != hipSuccess) return -1;
+        if (!w.verify_ev.create()) return -1;
         if (hipMalloc((void **)&w.verify_res, 64) != hipSuccess || hipMemset(w.verify_res, 0, 64) != hipSuccess)
             return -1;
         for (auto &e : w.chk_done)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return -1;
+            if (!e.create()) return -1;
         w.streams_ok = true;
     }
     for (int i = 0; i < npipes && i < WF_MAX_PIPES; ++i) {
@@ -234,9 +237,8 @@ int ensure_streams(Workspace &w, int npipes)
         if (p.stream) continue;
         if (hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking) != hipSuccess) return -1;
         if (hipHostMalloc((void **)&p.host_count, 64) != hipSuccess) return -1;
-        if (hipEventCreateWithFlags(&p.join, hipEventDisableTiming) != hipSuccess) return -1;
+        if (!p.join.create() || !p.long_done.create()) return -1;
         if (hipEventCreateWithFlags(&p.fin_done, hipEventDisableTiming) != hipSuccess) return -1;
-        if (hipEventCreateWithFlags(&p.long_done, hipEventDisableTiming) != hipSuccess) return -1;
         for (auto &e : p.ev)
             if (hipEventCreate(&e) != hipSuccess) return -1;
         hipLaunchKernelGGL(wf_bind_stream, dim3(1), dim3(64), 0, p.stream);
@@ -304,6 +306,82 @@ int resolve_profiles(Workspace &w)
     return 0;
 }
 
+// The blob's layout, every array named once: carve(p, n) gives p the next 256-byte-aligned offset and moves
+// on by n entries of p's element type, or of `entry` bytes where an entry is not one element; zero() also
+// lists the array among those that start as zeros.  Without a base it only sizes (the pointers come out null).
+struct Carver {
+    char *base;
+    size_t off = 0;
+    std::vector<std::pair<size_t, size_t>> zeroed; // {offset, bytes}
+    template <typename T>
+    void operator()(T *&p, size_t n, size_t entry = sizeof(T))
+    {
+        p = base ? (T *)(base + off) : nullptr;
+        off += (n * entry + 255) & ~(size_t)255;
+    }
+    template <typename T>
+    void zero(T *&p, size_t n, size_t entry = sizeof(T))
+    {
+        zeroed.emplace_back(off, n * entry);
+        (*this)(p, n, entry);
+    }
+};
+
+// lays the blob at `base` out into every pipeline's WfState and the workspace's own pointers (per-call
+// fields zero: each launch sets its own); returns the pass: the blob's size (off) and its zeroed arrays
+Carver carve_blob(Workspace &w, char *base, size_t slots, size_t spill_threads, int spill_pipes)
+{
+    Carver carve{base};
+    const size_t ray = 2 * sizeof(RtF4); // a queued ray: {o.xyz, -}, {d.xyz, -}
+    WfState st{};
+    st.spill_threads = (int)spill_threads;
+    st.long_cap = (uint32_t)slots;
+    st.linger = WF_FIN_LINGER;
+    // per pixel
+    carve(st.passes_left, slots);
+    carve(st.flags, slots);
+    carve(st.T, slots);
+    carve(st.L, slots);
+    carve(st.cont, slots);
+    carve(st.snorm, slots);
+    carve(st.rp, slots);
+    carve(st.light, slots);
+    carve(st.ro, slots);
+    carve(st.e_sh, slots);
+    carve(st.e_ext, slots);
+    carve.zero(st.pxo, slots); // no pixel out
+    carve.zero(st.heavy, slots, 1); // no pixel heavy or listed yet
+    carve.zero(st.listed, slots);
+    carve(w.heavy_list, slots); // (WfState.heavy_list: set per call by launch_whole_now)
+    carve.zero(st.heavy_n, 64);
+    // long-path hand-off (shared by the pipelines), wf_long's stack-free wide traversal needs no spill
+    carve(st.long_ent, slots);
+    carve(st.long_ray, slots, ray);
+    carve(st.long_ctr, 64);
+    carve(st.ret_ring, slots);
+    carve(st.ret_ctr, 64);
+    uint32_t *ctl; // 256 control bytes: the producer words, the guard's counters (+64), the chain flag (+128)
+    carve.zero(ctl, 64);
+    if (ctl) {
+        w.fin_live = ctl;
+        w.chk_ctr = ctl + 16;
+        st.chain_flag = ctl + 32;
+    }
+    // per pipeline (path lists sized for every pixel: a pipeline never holds
+    // more; ray queues for two rays per path: a shadow and an extension ray)
+    for (int i = 0; i < WF_MAX_PIPES; ++i) {
+        WfState &ps = w.pipe[i].st = st;
+        carve(ps.q_slot[0], slots);
+        carve(ps.q_slot[1], slots);
+        carve(ps.q_ray[0], 2 * slots, ray);
+        carve(ps.q_ray[1], 2 * slots, ray);
+        carve(ps.hits, 2 * slots);
+        carve(ps.counts, 64);
+        if (i < spill_pipes) carve(ps.spill, spill_threads * WF_SPILL_ENTRIES);
+    }
+    return carve;
+}
+
 int ensure(Workspace &w, size_t slots, int grid, int npipes)
 {
     if (ensure_streams(w, npipes > WF_PIPES_DEFAULT ? npipes : WF_PIPES_DEFAULT) != 0) return -1;
@@ -317,97 +395,15 @@ int ensure(Workspace &w, size_t slots, int grid, int npipes)
         (void)hipFree(w.blob);
     }
     w.blob = nullptr;
+    w.slots = 0; // (nothing to reuse if the allocation below fails)
     const size_t spill_threads = (size_t)grid * WF_BLOCK;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    // per pixel
-    const size_t o_pl = take(slots * 4), o_fl = take(slots * 4), o_T = take(slots * 12), o_L = take(slots * 12),
-                 o_c = take(slots * 12), o_n = take(slots * 12), o_rp = take(slots * 12), o_li = take(slots * 4),
-                 o_ro = take(slots * 12), o_es = take(slots * 4), o_ee = take(slots * 4), o_px = take(slots * 4),
-                 o_hv = take(slots), o_ls = take(slots * 4), o_hl = take(slots * 4), o_hn = take(256);
-    // long-path hand-off (shared by the pipelines), wf_long's stack-free wide traversal needs no spill
-    const size_t o_le = take(slots * 8), o_lr = take(slots * 32), o_lc = take(256), o_rr = take(slots * 8),
-                 o_rc = take(256), o_ctl = take(256);
-    // per pipeline (path lists sized for every pixel: a pipeline never holds
-    // more; ray queues for two rays per path: a shadow and an extension ray)
-    size_t o_qs0[WF_MAX_PIPES], o_qs1[WF_MAX_PIPES], o_qr0[WF_MAX_PIPES], o_qr1[WF_MAX_PIPES], o_h[WF_MAX_PIPES],
-        o_cnt[WF_MAX_PIPES], o_sp[WF_MAX_PIPES];
-    for (int i = 0; i < WF_MAX_PIPES; ++i) {
-        o_qs0[i] = take(slots * 4);
-        o_qs1[i] = take(slots * 4);
-        o_qr0[i] = take(2 * slots * 32);
-        o_qr1[i] = take(2 * slots * 32);
-        o_h[i] = take(2 * slots * 16);
-        o_cnt[i] = take(256);
-        o_sp[i] = i < spill_pipes ? take(spill_threads * 8 * WF_SPILL_ENTRIES) : 0;
-    }
-    if (hipMalloc(&w.blob, off) != hipSuccess) {
+    if (hipMalloc(&w.blob, carve_blob(w, nullptr, slots, spill_threads, spill_pipes).off) != hipSuccess) {
         w.blob = nullptr;
         return -1;
     }
-    char *b = (char *)w.blob;
-    if (hipMemset(b + o_px, 0, slots * 4) != hipSuccess) return -1; // no pixel out
-    if (hipMemset(b + o_hv, 0, slots) != hipSuccess || hipMemset(b + o_ls, 0, slots * 4) != hipSuccess ||
-        hipMemset(b + o_hn, 0, 256) != hipSuccess)
-        return -1; // no pixel heavy or listed yet
-    if (hipMemset(b + o_ctl, 0, 256) != hipSuccess) return -1;
-    w.fin_live = (uint32_t *)(b + o_ctl);
-    w.chk_ctr = (uint32_t *)(b + o_ctl + 64);
+    for (const auto &z : carve_blob(w, (char *)w.blob, slots, spill_threads, spill_pipes).zeroed)
+        if (hipMemset((char *)w.blob + z.first, 0, z.second) != hipSuccess) return -1;
     w.chain_open = false;
-    for (int i = 0; i < WF_MAX_PIPES; ++i) {
-        WfState &st = w.pipe[i].st;
-        st.passes_left = (int *)(b + o_pl);
-        st.flags = (uint32_t *)(b + o_fl);
-        st.T = (Vec3D *)(b + o_T);
-        st.L = (Vec3D *)(b + o_L);
-        st.cont = (Vec3D *)(b + o_c);
-        st.snorm = (Vec3D *)(b + o_n);
-        st.rp = (Vec3D *)(b + o_rp);
-        st.light = (int *)(b + o_li);
-        st.ro = (Vec3D *)(b + o_ro);
-        st.e_sh = (uint32_t *)(b + o_es);
-        st.e_ext = (uint32_t *)(b + o_ee);
-        st.q_slot[0] = (uint32_t *)(b + o_qs0[i]);
-        st.q_slot[1] = (uint32_t *)(b + o_qs1[i]);
-        st.q_ray[0] = (RtF4 *)(b + o_qr0[i]);
-        st.q_ray[1] = (RtF4 *)(b + o_qr1[i]);
-        st.hits = (RtF4 *)(b + o_h[i]);
-        st.counts = (uint32_t *)(b + o_cnt[i]);
-        st.spill = i < spill_pipes ? (uint2 *)(b + o_sp[i]) : nullptr;
-        st.spill_threads = (int)spill_threads;
-        st.long_ctr = (uint32_t *)(b + o_lc);
-        st.long_ent = (unsigned long long *)(b + o_le);
-        st.long_ray = (RtF4 *)(b + o_lr);
-        st.long_depth = 0;
-        st.long_cap = (uint32_t)slots;
-        st.long_return = 0;
-        st.ret_ring = (unsigned long long *)(b + o_rr);
-        st.ret_ctr = (uint32_t *)(b + o_rc);
-        st.linger = WF_FIN_LINGER;
-        st.pxo = (uint32_t *)(b + o_px);
-        st.heavy = (uint8_t *)(b + o_hv);
-        st.listed = (uint32_t *)(b + o_ls);
-        st.heavy_list = nullptr; // (set per call by launch_whole)
-        w.heavy_list = (uint32_t *)(b + o_hl);
-        st.heavy_n = (uint32_t *)(b + o_hn);
-        st.fin_live = nullptr;
-        st.chain_flag = (uint32_t *)(b + o_ctl + 128);
-        st.fresh = 0;
-        st.fresh_n = 0;
-        st.span = nullptr;
-        st.call_id = 0;
-        st.chk = nullptr; // (whole-call mode only: launch_whole)
-        st.chk_ctr = nullptr;
-        st.chk_mask = 0;
-        st.chk_cap = 0;
-        st.chk_fault = 0;
-        st.debug_quit = 0;
-        st.long_wide = 0;
-    }
     w.slots = slots;
     w.grid = grid;
     w.spill_pipes = spill_pipes;
@@ -428,10 +424,8 @@ int launch_verify(Workspace &w, hipStream_t stream)
     const int blocks = (int)std::min<size_t>((w.slots + WF_BLOCK - 1) / WF_BLOCK, 1024);
     hipLaunchKernelGGL(wf_verify, dim3(blocks), dim3(WF_BLOCK), 0, stream, w.pipe[0].st, (uint32_t)w.slots,
                        w.verify_res, w.last.fr.dev_stats);
-    if (hipGetLastError() != hipSuccess) return -1;
     // (every later launch on the workspace waits for it: join_all; and so does the host's read of its result)
-    if (hipEventRecord(w.verify_ev, stream) != hipSuccess) return -1;
-    w.verify_rec = true;
+    if (!w.verify_ev.record(stream)) return -1;
     w.verify_unread = true;
     return 0;
 }
@@ -443,13 +437,7 @@ int launch_verify(Workspace &w, hipStream_t stream)
 int join_all(Workspace &w, hipStream_t stream)
 {
     if (launch_drain(w) != 0) return -1;
-    if (w.verify_rec && hipStreamWaitEvent(stream, w.verify_ev, 0) != hipSuccess) return -1;
-    for (int pi = 0; pi < WF_MAX_PIPES; ++pi) {
-        Pipe &p = w.pipe[pi];
-        if (p.joined && hipStreamWaitEvent(stream, p.join, 0) != hipSuccess) return -1;
-        if (p.long_rec && hipStreamWaitEvent(stream, p.long_done, 0) != hipSuccess) return -1;
-    }
-    if (w.recorded && hipStreamWaitEvent(stream, w.long_ev, 0) != hipSuccess) return -1;
+    if (!each_tail(w, [&](SerialEvent &e) { return e.wait_on(stream); })) return -1;
     return launch_verify(w, stream);
 }
 
@@ -533,10 +521,41 @@ int launch_long(Pipe &lp, hipEvent_t after, const WholeCall &c, const WfState &s
 {
     if (hipStreamWaitEvent(lp.stream, after, 0) != hipSuccess) return -1;
     WF_LAUNCH_COUNT(count, wf_long, dim3(WF_LONG_BLOCKS), dim3(WF_BLOCK), lp.stream, c.sc, c.fr, c.cam, st, 1);
-    if (hipGetLastError() != hipSuccess) return -1;
-    if (hipEventRecord(lp.long_done, lp.stream) != hipSuccess) return -1;
-    lp.long_rec = true;
+    return lp.long_done.record(lp.stream) ? 0 : -1;
+}
+
+// the guard's record buffer holds `cap` records per parity (regrown for more: after every wf_check that
+// reads the old records)
+int ensure_records(Workspace &w, uint32_t cap)
+{
+    if (cap <= w.chk_cap) return 0;
+    if (w.chk) {
+        if (hipDeviceSynchronize() != hipSuccess) return -1;
+        (void)hipFree(w.chk);
+        w.chk = nullptr;
+        w.chk_cap = 0;
+    }
+    if (hipMalloc((void **)&w.chk, 2 * (size_t)cap * 3 * sizeof(RtF4)) != hipSuccess) {
+        w.chk = nullptr;
+        return -1;
+    }
+    w.chk_cap = cap;
     return 0;
+}
+
+// RT_DEBUG_CALL_LOG: the hand-off's counters once the finisher on `s` is done (`what`: the call or the drain)
+void call_log(const char *what, unsigned long long seq, hipStream_t s, const WfState &st)
+{
+    (void)hipStreamSynchronize(s);
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    uint32_t lc[4] = {}, rc[7] = {};
+    (void)hipMemcpy(lc, st.long_ctr, sizeof lc, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(rc, st.ret_ctr, sizeof rc, hipMemcpyDeviceToHost);
+    fprintf(stderr,
+            "[wf] %s %llu finisher done t %.4f; long entries %u claimed %u running %u; returns reserved %u claimed %u, "
+            "finisher waves alive %u, pixels out %u; owed passes: most %u, pixels %u\n",
+            what, seq, ts.tv_sec + ts.tv_nsec * 1e-9, lc[0], lc[1], lc[3], rc[0], rc[2], rc[1], rc[3], rc[5], rc[6]);
 }
 
 // The whole call in one persistent finisher (bounded traversal, the default):
@@ -592,36 +611,12 @@ int launch_whole_now(Workspace &w, const WholeCall &c)
     st.linger = overlap ? 0ull : WF_FIN_LINGER;
     st.chk_mask = check_mask;
     // the guard's records per call parity (the call two later reuses them after this call's wf_check),
-    // sized from the call's rays: <= 8 rays per sample (deep paths go to wf_long; owed passes are few)
-    // / the sampling interval, so a small frame does not hold the 2 x 4M-record maximum
+    // sized from the call's rays (wf_check_grid.h); wf_check's grid follows the same estimate
     const int par = (int)(w.call_seq & 1);
-    unsigned long long chk_want = 0; // the most records the call is sized for (wf_check's grid follows it)
-    if (check_mask != 0xFFFFFFFFu) {
-        // (every ray recorded — check_interval 1, the tests' setting — leaves that average no slack: sized for the
-        // most a sample can trace before its hand-off, an extension and a shadow ray per bounce, up to
-        // WF_CHECK_CAP — a frame beyond WF_CHECK_CAP / (2 * depth + 2) samples per call can still drop records,
-        // which check_dropped reports)
-        const unsigned long long per_sample =
-            check_mask == 0u ? 2ull * (unsigned long long)(long_depth > 0 ? long_depth : RT_DEEP_PATH) + 2ull : 8ull;
-        const unsigned long long want = (unsigned long long)slots * (unsigned long long)fr.passes * per_sample /
-                                        ((unsigned long long)check_mask + 1ull);
-        chk_want = want;
-        uint32_t cap = 1u << 16;
-        while (cap < want && cap < WF_CHECK_CAP) cap <<= 1;
-        if (cap > w.chk_cap) { // (grown: after every wf_check that reads the old records)
-            if (w.chk) {
-                if (hipDeviceSynchronize() != hipSuccess) return -1;
-                (void)hipFree(w.chk);
-                w.chk = nullptr;
-                w.chk_cap = 0;
-            }
-            if (hipMalloc((void **)&w.chk, 2 * (size_t)cap * 3 * sizeof(RtF4)) != hipSuccess) {
-                w.chk = nullptr;
-                return -1;
-            }
-            w.chk_cap = cap;
-        }
-    }
+    unsigned long long chk_want = 0;
+    if (ensure_records(w, wf_check_records(slots, (unsigned long long)fr.passes, check_mask,
+                                           long_depth > 0 ? long_depth : RT_DEEP_PATH, WF_CHECK_CAP, &chk_want)) != 0)
+        return -1;
     st.chk = check_mask == 0xFFFFFFFFu ? nullptr : w.chk + 3 * (size_t)w.chk_cap * (size_t)par;
     st.chk_cap = w.chk_cap;
     st.chk_ctr = w.chk_ctr + par;
@@ -662,7 +657,7 @@ int launch_whole_now(Workspace &w, const WholeCall &c)
     if (st.fin_live && hipMemsetD32Async((hipDeviceptr_t)st.fin_live, (int)(fgrid * (WF_BLOCK / 64)), 1, s) != hipSuccess)
         return -1;
     if (st.chk) { // (this parity's records: after the wf_check that last read them)
-        if (w.chk_rec[par] && hipStreamWaitEvent(s, w.chk_done[par], 0) != hipSuccess) return -1;
+        if (!w.chk_done[par].wait_on(s)) return -1;
         if (hipMemsetAsync(st.chk_ctr, 0, 4, s) != hipSuccess) return -1;
     }
     if (long_return && hipMemsetD32Async((hipDeviceptr_t)st.chain_flag, overlap ? 1 : 0, 1, s) != hipSuccess) return -1;
@@ -692,7 +687,7 @@ int launch_whole_now(Workspace &w, const WholeCall &c)
     const bool fin_first = lp && !long_first && (debug & RT_DEBUG_SERIAL_FIN_FIRST);
     const hipEvent_t long_after = fin_first ? pp.fin_done : w.fin_ready;
     if (long_first &&
-        (launch_long(*lp, long_after, c, st, c.count) != 0 || hipStreamWaitEvent(s, lp->long_done, 0) != hipSuccess))
+        (launch_long(*lp, long_after, c, st, c.count) != 0 || !lp->long_done.wait_on(s)))
         return -1;
     if (launch_finisher(w, fgrid, s, c, st, c.count) != 0) return -1;
     if (hipEventRecord(pp.fin_done, s) != hipSuccess) return -1;
@@ -715,39 +710,22 @@ int launch_whole_now(Workspace &w, const WholeCall &c)
             return -1;
         }
         hipLaunchKernelGGL(wf_check, dim3(cgrid), dim3(WF_BLOCK), 0, cp.stream, sc, cs, fr.dev_stats);
-        if (hipGetLastError() != hipSuccess) return -1;
-        if (hipEventRecord(w.chk_done[par], cp.stream) != hipSuccess || hipEventRecord(cp.join, cp.stream) != hipSuccess)
-            return -1;
-        w.chk_rec[par] = true;
-        cp.joined = true;
+        if (!w.chk_done[par].record(cp.stream) || !cp.join.record(cp.stream)) return -1;
     }
-    if (hipEventRecord(pp.join, s) != hipSuccess) return -1;
-    pp.joined = true;
+    if (!pp.join.record(s)) return -1;
     // join: unless the call overlaps the next one, the caller's stream continues after the
     // finisher and after its wf_long (the guard's wf_check touches no frame data: its statistics
     // are read by rt_deviation_stats, which joins it)
     if (!overlap) {
-        if (hipStreamWaitEvent(stream, pp.join, 0) != hipSuccess) return -1;
-        if (lp && hipStreamWaitEvent(stream, lp->long_done, 0) != hipSuccess) return -1;
+        if (!pp.join.wait_on(stream)) return -1;
+        if (lp && !lp->long_done.wait_on(stream)) return -1;
     }
     w.chain_open = overlap && long_return;
     w.verify_pending = w.verify_pending || long_return;
     w.key = key;
     w.last = c;
     w.last.fr.reset = 0;
-    if (debug & RT_DEBUG_CALL_LOG) {
-        (void)hipStreamSynchronize(s);
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        uint32_t lc[4] = {}, rc4[7] = {};
-        (void)hipMemcpy(lc, st.long_ctr, sizeof lc, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(rc4, st.ret_ctr, sizeof rc4, hipMemcpyDeviceToHost);
-        fprintf(stderr,
-                "[wf] call %llu%s finisher done t %.4f; long entries %u claimed %u running %u; returns reserved %u "
-                "claimed %u, finisher waves alive %u, pixels out %u; owed passes: most %u, pixels %u\n",
-                w.call_seq, chained ? " (chained)" : "", ts.tv_sec + ts.tv_nsec * 1e-9, lc[0], lc[1], lc[3], rc4[0],
-                rc4[2], rc4[1], rc4[3], rc4[5], rc4[6]);
-    }
+    if (debug & RT_DEBUG_CALL_LOG) call_log(chained ? "chained call" : "call", w.call_seq, s, st);
     if (st.long_log && !overlap) return debug_long_log(long_log_buf);
     return 0;
 }
@@ -826,18 +804,9 @@ int launch_drain(Workspace &w)
     if (hipEventRecord(w.fin_ready, s) != hipSuccess) return -1;
     if (launch_finisher(w, fgrid, s, c, st, false) != 0) return -1;
     if (launch_long(w.pipe[1], w.fin_ready, c, st, false) != 0) return -1;
-    if (hipEventRecord(pp.join, s) != hipSuccess) return -1;
-    pp.joined = true;
+    if (!pp.join.record(s)) return -1;
     w.verify_pending = true;
-    if (c.debug & RT_DEBUG_CALL_LOG) {
-        (void)hipStreamSynchronize(s);
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        uint32_t rc[7] = {};
-        (void)hipMemcpy(rc, st.ret_ctr, sizeof rc, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[wf] drain done t %.4f; returns reserved %u claimed %u, pixels out %u; owed passes: most %u, pixels %u\n",
-                ts.tv_sec + ts.tv_nsec * 1e-9, rc[0], rc[2], rc[3], rc[5], rc[6]);
-    }
+    if (c.debug & RT_DEBUG_CALL_LOG) call_log("drain", w.call_seq, s, st);
     return 0;
 }
 
@@ -927,17 +896,15 @@ int launch_queue(Workspace &w, int dev, const RtDevScene &sc, const RtDevFrame &
         std::lock_guard<std::mutex> g(long_mu);
         if (long_final) return 0;
         if (!final) {
-            const hipError_t q = hipEventQuery(w.long_ev);
+            const hipError_t q = w.long_ev.query();
             if (q == hipErrorNotReady) return 0;
             if (q != hipSuccess) return -1;
         }
         const int fin = final ? 1 : 0;
         WF_LAUNCH_COUNT(count, wf_long, dim3(WF_LONG_BLOCKS), dim3(WF_BLOCK), stream, sc, fr, cam, lst, fin);
-        if (hipGetLastError() != hipSuccess) return -1;
+        if (!w.long_ev.record(stream)) return -1;
         long_final = final;
         ++n_slices;
-        if (hipEventRecord(w.long_ev, stream) != hipSuccess) return -1;
-        w.recorded = true;
         return 0;
     };
     std::atomic<int> producing(npipes);
@@ -1063,8 +1030,7 @@ int launch_queue(Workspace &w, int dev, const RtDevScene &sc, const RtDevFrame &
             }
         }
         if (rc != 0) return rc;
-        if (hipEventRecord(pp.join, s) != hipSuccess) return -1;
-        pp.joined = true;
+        if (!pp.join.record(s)) return -1;
         if (prof) {
             if (!mark(4) || hipEventSynchronize(pp.ev[4]) != hipSuccess) return -1;
             P.trace_launches = P.shade_launches = P.iterations;
@@ -1095,7 +1061,7 @@ int launch_queue(Workspace &w, int dev, const RtDevScene &sc, const RtDevFrame &
         if (rcs[pi] != 0) return rcs[pi];
     // join: the caller's stream continues after every pipeline
     for (int pi = 0; pi < npipes; ++pi)
-        if (hipStreamWaitEvent(stream, w.pipe[pi].join, 0) != hipSuccess) return -1;
+        if (!w.pipe[pi].join.wait_on(stream)) return -1;
     if (prof) {
         RtProfile P{};
         for (int pi = 0; pi < npipes; ++pi) { // kernel times summed over the (concurrent) pipelines
@@ -1138,10 +1104,10 @@ int launch_queue(Workspace &w, int dev, const RtDevScene &sc, const RtDevFrame &
 // before anything else in the process (RCCL's streams in a multi-GPU run)
 int rt_wavefront_device_init()
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
     rt_register_shutdown();
-    return ensure_streams(workspace(dev), WF_PIPES_DEFAULT);
+    std::lock_guard<std::mutex> g(g_ws.mu);
+    Workspace *w = g_ws.current();
+    return w ? ensure_streams(*w, WF_PIPES_DEFAULT) : -1;
 }
 
 static thread_local char g_incomplete[256];
@@ -1160,27 +1126,16 @@ int rt_wavefront_join(void *stream, int consume)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
-    Workspace *w = nullptr;
-    {
-        std::lock_guard<std::mutex> g(g_ws_mu);
-        auto it = g_ws.find(dev);
-        if (it == g_ws.end() || !it->second) return 0;
-        w = it->second;
-    }
+    std::lock_guard<std::mutex> g(g_ws.mu);
+    Workspace *w = g_ws.find(); // (a device that never rendered: nothing to join, and nothing is made)
+    if (!w) return 0;
     if (stream) return join_all(*w, (hipStream_t)stream);
     if (launch_drain(*w) != 0) return -1;
-    for (int pi = 0; pi < WF_MAX_PIPES; ++pi) {
-        Pipe &p = w->pipe[pi];
-        if (p.joined && hipEventSynchronize(p.join) != hipSuccess) return -1;
-        if (p.long_rec && hipEventSynchronize(p.long_done) != hipSuccess) return -1;
-    }
-    if (w->recorded && hipEventSynchronize(w->long_ev) != hipSuccess) return -1;
-    if (w->verify_pending) {
-        const hipStream_t s = w->pipe[0].stream; // (idle: everything above is done)
-        if (launch_verify(*w, s) != 0) return -1;
-    }
-    // (the last check may run on a caller's stream: its result is read after it)
-    if (w->verify_rec && hipEventSynchronize(w->verify_ev) != hipSuccess) return -1;
+    if (!each_tail(*w, [](SerialEvent &e) { return e.wait_host(); })) return -1;
+    // the hand-off check on pipeline 0's stream (idle: everything above is done)
+    if (launch_verify(*w, w->pipe[0].stream) != 0) return -1;
+    // (the last check may have run on a caller's stream: its result is read after it)
+    if (!w->verify_ev.wait_host()) return -1;
     if (!w->verify_unread) return 0;
     uint32_t r[5] = {};
     if (hipMemcpy(r, w->verify_res, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) return -1;
@@ -1198,39 +1153,27 @@ int rt_wavefront_join(void *stream, int consume)
 }
 
 // rt_shutdown: every stream, event and device blob of every device's
-// workspace, in reverse creation order, after the device work is done
+// workspace, after its device work is done: the blobs, the events, then each
+// pipeline's stream in reverse creation order
 void rt_wavefront_shutdown()
 {
-    std::lock_guard<std::mutex> g(g_ws_mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto &kv : g_ws) {
-        Workspace *w = kv.second;
-        if (!w) continue;
-        if (hipSetDevice(kv.first) != hipSuccess) continue;
-        if (w->blob) (void)launch_drain(*w); // (an open chain's wf_longs leave only after its drain)
+    g_ws.shutdown([](Workspace &w) {
+        if (w.blob) (void)launch_drain(w); // (an open chain's wf_longs leave only after its drain)
         (void)hipDeviceSynchronize();
-        if (w->blob) (void)hipFree(w->blob);
-        for (void *p : {(void *)w->chk, (void *)w->verify_res, (void *)w->long_log_buf, (void *)w->spans})
+        for (void *p : {w.blob, (void *)w.chk, (void *)w.verify_res, (void *)w.long_log_buf, (void *)w.spans})
             if (p) (void)hipFree(p);
+        (void)each_tail(w, [](SerialEvent &e) { return e.destroy(), true; });
+        for (SerialEvent &e : w.chk_done) e.destroy();
         for (int i = WF_MAX_PIPES - 1; i >= 0; --i) {
-            Pipe &p = w->pipe[i];
-            for (auto &e : p.ev)
+            Pipe &p = w.pipe[i];
+            for (hipEvent_t e : {p.ev[5], p.ev[4], p.ev[3], p.ev[2], p.ev[1], p.ev[0], p.fin_done})
                 if (e) (void)hipEventDestroy(e);
-            if (p.long_done) (void)hipEventDestroy(p.long_done);
-            if (p.fin_done) (void)hipEventDestroy(p.fin_done);
-            if (p.join) (void)hipEventDestroy(p.join);
             if (p.host_count) (void)hipHostFree(p.host_count);
             if (p.stream) (void)hipStreamDestroy(p.stream);
         }
-        for (hipEvent_t e : {w->verify_ev, w->chk_done[1], w->chk_done[0], w->ev1, w->ev0, w->long_ev, w->fin_ready,
-                             w->fork})
+        for (hipEvent_t e : {w.ev1, w.ev0, w.fin_ready, w.fork})
             if (e) (void)hipEventDestroy(e);
-        delete w;
-        kv.second = nullptr;
-    }
-    g_ws.clear();
-    (void)hipSetDevice(cur);
+    });
 }
 
 extern "C" int rt_last_profile(RtProfile *out)
@@ -1238,14 +1181,14 @@ extern "C" int rt_last_profile(RtProfile *out)
     if (!out) return RT_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return RT_E_HIP;
-    std::lock_guard<std::mutex> g(g_ws_mu);
-    auto it = g_ws.find(dev);
-    if (it == g_ws.end() || !it->second) {
+    std::lock_guard<std::mutex> g(g_ws.mu);
+    Workspace *w = g_ws.find();
+    if (!w) {
         *out = RtProfile{};
         return RT_OK;
     }
-    if (flush_pending(*it->second) != 0 || resolve_profiles(*it->second) != 0) return RT_E_HIP;
-    *out = it->second->prof;
+    if (flush_pending(*w) != 0 || resolve_profiles(*w) != 0) return RT_E_HIP;
+    *out = w->prof;
     return RT_OK;
 }
 
@@ -1254,11 +1197,11 @@ extern "C" int rt_profile_history(RtProfile *out, int cap, int *count, int reset
     if ((!out && cap > 0) || cap < 0 || !count) return RT_E_INVALID;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return RT_E_HIP;
-    std::lock_guard<std::mutex> g(g_ws_mu);
-    auto it = g_ws.find(dev);
+    std::lock_guard<std::mutex> g(g_ws.mu);
     *count = 0;
-    if (it == g_ws.end() || !it->second) return RT_OK;
-    Workspace &w = *it->second;
+    Workspace *wp = g_ws.find();
+    if (!wp) return RT_OK;
+    Workspace &w = *wp;
     if (flush_pending(w) != 0 || resolve_profiles(w) != 0) return RT_E_HIP;
     *count = (int)w.prof_hist.size();
     for (int i = 0; i < cap && i < *count; ++i) out[i] = w.prof_hist[i];
@@ -1273,8 +1216,9 @@ int rt_launch_wavefront(const RtDevScene &sc, const RtDevFrame &fr, const RtDevC
     if (trace_kind == 1 && sc.index_count >= (1 << 26)) trace_kind = 3;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
-    Workspace &w = workspace(dev);
     rt_register_shutdown();
+    std::lock_guard<std::mutex> g(g_ws.mu);
+    Workspace &w = g_ws.slots[dev];
     const size_t slots = (size_t)fr.width * fr.height;
     const bool count = fr.counters != nullptr;
     // the queue trace launches run the BVH-bounded traversal (counting calls: the KD one, whose counters are the reference's)

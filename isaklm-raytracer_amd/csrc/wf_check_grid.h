@@ -1,6 +1,6 @@
-// The launch shape of wf_check, the run-time guard's KD re-trace (wavefront.hip;
-// DESIGN.md §5 "Run-time guard").  Plain host C++, so that a CPU test can call it
-// (tests/native/check_grid_check.cpp).
+// The sizes of the run-time guard (wavefront.hip; DESIGN.md §5 "Run-time guard"):
+// the launch shape of wf_check, its KD re-trace, and the records a call may hold.
+// Plain host C++, so that a CPU test can call it (tests/native/check_grid_check.cpp).
 #pragma once
 #include <cstdint>
 
@@ -29,4 +29,24 @@ static inline int wf_check_grid(bool chained, unsigned long long want, uint32_t 
         blocks = b > blocks ? b : blocks;
     }
     return blocks > (unsigned long long)limit ? limit : (int)blocks;
+}
+
+// The records a whole call's guard is sized for: `want`, the host's estimate of the rays it records, and
+// the return value, the record buffer's capacity per parity for it (0 and 0: the guard is off,
+// check_mask 0xFFFFFFFF).  One ray in check_mask + 1 is recorded, of at most 8 rays per sample: deep
+// paths go to wf_long, owed passes are few, so a small frame does not hold the 2 x max_cap maximum.
+// Every ray recorded (check_mask 0, the tests' check_interval 1) leaves that average no slack: sized for
+// the most a sample can trace before its hand-off at `depth` bounces, an extension and a shadow ray per
+// bounce.  The capacity is a power of two from 2^16 up to max_cap (WF_CHECK_CAP): a frame beyond max_cap
+// records per call can still drop some, which RtDeviations.check_dropped reports.
+static inline uint32_t wf_check_records(unsigned long long slots, unsigned long long passes, uint32_t check_mask,
+                                        int depth, uint32_t max_cap, unsigned long long *want)
+{
+    *want = 0;
+    if (check_mask == 0xFFFFFFFFu) return 0;
+    const unsigned long long per_sample = check_mask == 0u ? 2ull * (unsigned long long)depth + 2ull : 8ull;
+    *want = slots * passes * per_sample / ((unsigned long long)check_mask + 1ull);
+    uint32_t cap = 1u << 16;
+    while (cap < *want && cap < max_cap) cap <<= 1;
+    return cap;
 }

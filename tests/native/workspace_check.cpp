@@ -1,5 +1,6 @@
-// Drives rt_workspace.h's slot table, serial event and shutdown walk with a stub resource and stub HIP entry
-// points (no runtime linked): built with -fsanitize=address,undefined.
+// Drives rt_workspace.h's slot table (both lookups), serial event (made on first use or ahead of it, waited
+// for, queried) and shutdown walk with a stub resource and stub HIP entry points (no runtime linked): built
+// with -fsanitize=address,undefined.
 #include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,8 +15,9 @@ namespace {
 int g_dev = 0, g_ndev = 4;
 int g_fail_set = -1; // a device hipSetDevice refuses
 std::set<int *> g_events; // live events (heap cells: a leak or double destroy is ASan's to find too)
-int g_stream_waits = 0, g_host_waits = 0, g_records = 0;
+int g_stream_waits = 0, g_host_waits = 0, g_records = 0, g_queries = 0;
 hipError_t g_launch_error = hipSuccess;
+hipError_t g_query_result = hipSuccess; // what the recorded work's state is
 } // namespace
 
 extern "C" {
@@ -53,6 +55,12 @@ hipError_t hipEventSynchronize(hipEvent_t e)
     assert(g_events.count((int *)e) == 1);
     ++g_host_waits;
     return hipSuccess;
+}
+hipError_t hipEventQuery(hipEvent_t e)
+{
+    assert(g_events.count((int *)e) == 1);
+    ++g_queries;
+    return g_query_result;
 }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t)
 {
@@ -147,6 +155,40 @@ int main()
     assert(use(t, 4));
     t.shutdown(release);
     assert(g_events.empty() && g_live_bufs == 0 && g_dev == 2);
+    // an event made ahead of its first use (the wavefront workspace's): once; nothing recorded is done
+    // without a runtime call, and neither wait calls one; recorded work's state is the runtime's
+    {
+        SerialEvent e;
+        const int sw = g_stream_waits, hw = g_host_waits;
+        assert(e.query() == hipSuccess && g_queries == 0 && g_events.empty());
+        assert(e.create() && g_events.size() == 1);
+        hipEvent_t first = e.ev;
+        assert(e.create() && e.ev == first && g_events.size() == 1);
+        assert(e.query() == hipSuccess && g_queries == 0);
+        assert(e.wait_on(nullptr) && e.wait_host() && g_stream_waits == sw && g_host_waits == hw);
+        assert(e.ev == first && g_events.size() == 1);
+        assert(e.record(nullptr));
+        g_query_result = hipErrorNotReady;
+        assert(e.query() == hipErrorNotReady && g_queries == 1);
+        g_query_result = hipErrorLaunchFailure;
+        assert(e.query() == hipErrorLaunchFailure && g_queries == 2);
+        g_query_result = hipSuccess;
+        assert(e.query() == hipSuccess && g_queries == 3);
+        assert(e.wait_on(nullptr) && g_stream_waits == sw + 1);
+        e.destroy();
+        assert(g_events.empty() && g_host_waits == hw + 1);
+    }
+    // a lookup that makes nothing (a join on a device that never rendered), then the slot current() made
+    {
+        DeviceSlots<Res> u;
+        std::lock_guard<std::mutex> g(u.mu);
+        g_dev = 1;
+        assert(u.find() == nullptr && u.slots.empty());
+        Res *made = u.current();
+        assert(made && u.find() == made && u.slots.size() == 1);
+        g_dev = 2;
+        assert(u.find() == nullptr && u.slots.size() == 1);
+    }
     // a table without an event (the deviation block's shape)
     DeviceSlots<int *> blocks;
     {
@@ -157,6 +199,7 @@ int main()
     }
     blocks.shutdown([](int *&p) { delete[] p; });
     assert(blocks.slots.empty());
-    printf("workspace_check OK: stream waits %d, host waits %d, records %d\n", g_stream_waits, g_host_waits, g_records);
+    printf("workspace_check OK: stream waits %d, host waits %d, records %d, queries %d\n", g_stream_waits, g_host_waits,
+           g_records, g_queries);
     return 0;
 }

@@ -393,6 +393,55 @@ def test_stream_join_then_render_on_another_stream(tmp_path):
     helpers.assert_bitwise(g.download(), ref, what="render on stream b after a join on stream a")
 
 
+def test_profile_reader_beside_a_rendering_thread():
+    """Calls on one device from several host threads are serialised by the
+    library (the workspace table's mutex, held by every entry point of
+    wavefront.hip until its launches are enqueued).  One thread issues eight
+    chained 1-pass calls (coalesced by default: recorded, not launched) and
+    joins; another reads the profile history in a loop meanwhile — each read
+    launches whatever batch is pending.  However the two interleave, the frame
+    is the oracle's 8 passes and the join reports nothing."""
+    import threading
+
+    run = helpers.GpuRun("room_small")
+    W, H = 48, 27
+    ref, _ = helpers.oracle_render(run.path, W, H, 8)
+    rt.join()
+    g = rt.GBuffer(W, H)
+    done = threading.Event()
+    status, reads, errors = [], [0], []
+
+    def render():
+        try:
+            rt.check(rt.lib().rt_set_device(0))
+            for c in range(8):
+                rt.render(run.dev, g, run.camera, 0 if c == 0 else 1,
+                          rt.options(W, H, 1, adaptive=False, kernel=WF, overlap=True))
+            status.append(rt.lib().rt_join(None))
+        except Exception as e:  # (reported by the asserts below, not lost with the thread)
+            errors.append(e)
+        finally:
+            done.set()
+
+    def read():
+        try:
+            rt.check(rt.lib().rt_set_device(0))
+            while not done.is_set():
+                rt.profile_history()
+                reads[0] += 1
+        except Exception as e:
+            errors.append(e)
+
+    threads = [threading.Thread(target=f) for f in (render, read)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    assert status == [0], status  # RT_OK
+    helpers.assert_bitwise(g.download(), ref, what=f"8 chained 1-pass calls beside {reads[0]} profile reads")
+
+
 def test_coalesced_chained_calls():
     """RtOptions.coalesce_passes: chained calls of fewer passes are recorded
     and launched as one chained call once the batch holds that many passes, or
