@@ -2,8 +2,12 @@
 (oracle/rt_oracle.c).  Used by tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg as the checker; never by the product path.
 
-Parity status: "parity unpinned" for radiance (the reference is unbuildable
-here; see rt_oracle.h and DESIGN.md §Parity).
+Parity status: pinned bit for bit to the reference's own source, which
+Makefile.ref compiles as host C++ where a copy of it is present (build() runs
+that recipe then; reference.py wraps the result; tests/test_reference_cpu.py
+compares).  Pinned is that source under IEEE arithmetic without contraction
+with the project's transcendentals; nvcc's FMA contraction and libdevice's
+transcendentals stay unpinned (rt_oracle.h).
 """
 import ctypes
 import os
@@ -31,8 +35,24 @@ class OrOptions(ctypes.Structure):
                 ("max_depth", ctypes.c_int), ("threads", ctypes.c_int)]
 
 
+REF_MAKEFILE = os.path.join(HERE, "Makefile.ref")
+
+
+def reference_source():
+    """Directory of the reference's source (the REF of Makefile.ref), or None where no copy of it is present."""
+    ref = os.environ.get("REF")
+    if not ref:
+        for line in open(REF_MAKEFILE):
+            if line.startswith("REF ?="):
+                ref = line.split("=", 1)[1].strip()
+    return ref if ref and os.path.exists(os.path.join(ref, "path_tracing.cuh")) else None
+
+
 def build():
     subprocess.run(["make", "-s", "-C", HERE], check=True)
+    ref = reference_source()
+    if ref:  # the reference's own source as libraries (oracle/_ref/); nothing to do where it is absent
+        subprocess.run(["make", "-s", "-C", HERE, "-f", "Makefile.ref", "REF=" + ref], check=True)
     return LIB_PATH
 
 

@@ -1,7 +1,7 @@
 /*
  * rt_oracle.c — TEST INFRASTRUCTURE ONLY (see rt_oracle.h for the parity
- * status: "parity unpinned" for radiance, the reference being unbuildable
- * here).
+ * status: pinned bit for bit to the reference's own source built as host
+ * C++, tests/test_reference_cpu.py).
  *
  * Plain-C restatement of INDA23PlusPlus/isaklm-raytracer's render path.
  * Every function cites the reference lines it restates (rt/ =

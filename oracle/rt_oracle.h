@@ -6,15 +6,17 @@
  * __graft_entry__.smoke() and as bench.py's cpu_baseline ("kind": "port").
  * Nothing in the product (isaklm-raytracer_amd/) links, loads or calls it.
  *
- * Parity status: the reference itself cannot be built in this image (its path
- * includes <cuda_runtime.h>, <device_launch_parameters.h>,
- * <cuda_gl_interop.h>, <surface_functions.h> and GLFW/GL; no CUDA toolkit is
- * installed and stand-in headers are not allowed), and the reference ships no
- * tests or fixtures for this path.  The restatement is therefore
- * "parity unpinned" for radiance; it is pinned where public known answers
- * exist (mt19937: C++ standard [rand.predef] 10000th output and the
- * reference-run seeds recorded in SURVEY §8c; .mat parsing against the
- * reference's own material files).  See DESIGN.md §Parity.
+ * Parity status: pinned to the reference's own source.  oracle/Makefile.ref
+ * compiles the reference's headers, where a copy of it is present, as host
+ * C++ into oracle/_ref/libref_rt.so (driver: ref_harness.cpp, stand-in CUDA
+ * and GLFW headers: ref_shim/), and tests/test_reference_cpu.py compares this
+ * restatement with it bit for bit: scene bytes, seeds, trace_ray,
+ * get_scattered_light, sample_direct_light, correct_color and whole frames.
+ * Its recorded results (tests/golden/reference/) pin the kernels in turn.
+ * Pinned is the reference's source under IEEE arithmetic without contraction
+ * and with the project's transcendentals (csrc/rt_libm.h).  Unpinned stays what
+ * cannot be known here: nvcc's default FMA contraction and libdevice's
+ * sinf/cosf/tanf/powf/erfinvf.  See DESIGN.md §3.
  */
 #ifndef RT_ORACLE_H
 #define RT_ORACLE_H

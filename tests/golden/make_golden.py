@@ -1,11 +1,11 @@
 """Regenerates tests/golden/oracle_regression.json.
 
-The reference cannot be built in this image (it needs the CUDA toolkit and
-GLFW/GL headers; see oracle/rt_oracle.h), so these vectors come from the CPU
-oracle (oracle/rt_oracle.c) and pin it against regressions; the GPU tests
-check the HIP path against the same vectors.  The reference-owned fixtures
-are the material files in tests/golden/materials/ (copied data) and the
-known answers quoted in tests/test_oracle.py.
+These vectors come from the CPU oracle (oracle/rt_oracle.c) and pin it against
+regressions; the GPU tests check the HIP path against the same vectors.  The
+reference-owned fixtures are the material files in tests/golden/materials/
+(copied data), the known answers quoted in tests/test_oracle.py and the
+results of the reference's own source in tests/golden/reference/
+(tests/golden/make_reference_golden.py).
 
 usage: python tests/golden/make_golden.py
 """

@@ -35,12 +35,8 @@ def _same(a, b):
     return (a.view(np.uint32) == b.view(np.uint32)) | both_nan
 
 
-def test_scatter_matches_independent_restatement():
-    """get_scattered_light (rt/path_tracing.cuh:151-219) on 60,000 random
-    samples covering every branch: metallic (fresnel_conductor), dielectric
-    specular from outside and inside (total internal reflection included),
-    transmission (refraction_direction, inside flips) and diffuse
-    (diffuse_direction); the FP64 island of microfacet_normal."""
+def scatter_inputs():
+    """the 60,000 inputs of the scatter comparison (shared with tests/test_reference_cpu.py)"""
     g = np.random.default_rng(1234)
     N = 60_000
     d = _unit(g, N)
@@ -58,12 +54,23 @@ def test_scatter_matches_independent_restatement():
     inside = g.uniform(size=N) < 0.4
     pos = g.uniform(-3, 3, (N, 3)).astype(f32)
     state = g.integers(0, 2 ** 32, N, dtype=np.uint64).astype(np.uint32)
+    return N, d, nrm, tan, bit, albedo, rough, ior, ext, transparent, inside, pos, state
 
-    o_pos, o_dir, o_w, o_type, o_in, o_rng = ind.scatter(d, inside, state, albedo, rough, ior, ext, transparent, pos,
-                                                         nrm, tan, bit)
+
+def scatter_samples(albedo, rough, ior, ext, transparent, pos, nrm, tan, bit):
+    """the inputs as or_scatter's sample[22] rows"""
+    smp = np.zeros((len(albedo), 22), f32)
+    smp[:, 0:3] = albedo
+    smp[:, 6], smp[:, 7], smp[:, 8], smp[:, 9] = rough, ior, ext, transparent.astype(f32)
+    smp[:, 10:13], smp[:, 13:16], smp[:, 16:19], smp[:, 19:22] = pos, nrm, tan, bit
+    return smp
+
+
+def oracle_scatter(d, smp, inside, state):
+    """or_scatter on every row -> (direction, weight, type, inside after, rng after)"""
+    N = len(d)
     L = oracle.lib()
     out = np.zeros(12, f32)
-    smp = np.zeros(22, f32)
     r_out, in_out, ty_out = ctypes.c_uint32(), ctypes.c_int(), ctypes.c_int()
     got_dir = np.zeros((N, 3), f32)
     got_w = np.zeros((N, 3), f32)
@@ -71,14 +78,27 @@ def test_scatter_matches_independent_restatement():
     got_in = np.zeros(N, bool)
     got_rng = np.zeros(N, np.uint32)
     for k in range(N):
-        smp[0:3] = albedo[k]
-        smp[6], smp[7], smp[8], smp[9] = rough[k], ior[k], ext[k], float(transparent[k])
-        smp[10:13], smp[13:16], smp[16:19], smp[19:22] = pos[k], nrm[k], tan[k], bit[k]
         dk = np.ascontiguousarray(d[k])
-        L.or_scatter(dk.ctypes.data, smp.ctypes.data, int(inside[k]), int(state[k]), out.ctypes.data,
+        sk = np.ascontiguousarray(smp[k])
+        L.or_scatter(dk.ctypes.data, sk.ctypes.data, int(inside[k]), int(state[k]), out.ctypes.data,
                      ctypes.byref(r_out), ctypes.byref(in_out), ctypes.byref(ty_out))
         got_dir[k], got_w[k] = out[3:6], out[6:9]
         got_t[k], got_in[k], got_rng[k] = ty_out.value, bool(in_out.value), r_out.value
+    return got_dir, got_w, got_t, got_in, got_rng
+
+
+def test_scatter_matches_independent_restatement():
+    """get_scattered_light (rt/path_tracing.cuh:151-219) on 60,000 random
+    samples covering every branch: metallic (fresnel_conductor), dielectric
+    specular from outside and inside (total internal reflection included),
+    transmission (refraction_direction, inside flips) and diffuse
+    (diffuse_direction); the FP64 island of microfacet_normal."""
+    N, d, nrm, tan, bit, albedo, rough, ior, ext, transparent, inside, pos, state = scatter_inputs()
+
+    o_pos, o_dir, o_w, o_type, o_in, o_rng = ind.scatter(d, inside, state, albedo, rough, ior, ext, transparent, pos,
+                                                         nrm, tan, bit)
+    smp = scatter_samples(albedo, rough, ior, ext, transparent, pos, nrm, tan, bit)
+    got_dir, got_w, got_t, got_in, got_rng = oracle_scatter(d, smp, inside, state)
     assert np.array_equal(got_t, o_type)
     assert np.array_equal(got_in, o_in)
     assert np.array_equal(got_rng, o_rng)
@@ -96,10 +116,8 @@ def test_scatter_matches_independent_restatement():
     assert tir.sum() > 1000 and np.all(o_type[tir] == ind.SPECULAR)
 
 
-def test_direct_light_matches_independent_restatement():
-    """sample_direct_light + random_point_in_triangle (rt/path_tracing.cuh:
-    222-265) at 4,000 surface points of the Cornell box (lit, occluded and
-    back-facing cases), the same shadow-ray tracer on both sides."""
+def direct_light_inputs():
+    """the shading points of the direct-light comparison (shared with tests/test_reference_cpu.py)"""
     path = helpers.scene_path("cornell")
     osc = oracle.OracleScene(path)
     tris_raw, _, _, lights, bounds = osc.arrays()
@@ -115,6 +133,15 @@ def test_direct_light_matches_independent_restatement():
     n = len(pos)
     assert n > 2000  # the box is open at the front
     state = g.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    return osc, tris, lights, pos, nrm, state
+
+
+def test_direct_light_matches_independent_restatement():
+    """sample_direct_light + random_point_in_triangle (rt/path_tracing.cuh:
+    222-265) at 4,000 surface points of the Cornell box (lit, occluded and
+    back-facing cases), the same shadow-ray tracer on both sides."""
+    osc, tris, lights, pos, nrm, state = direct_light_inputs()
+    n = len(pos)
 
     def trace(rays6):  # the Cornell box is untextured: a hit's emittance is its material's
         o = osc.trace_rays(rays6)

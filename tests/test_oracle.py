@@ -1,7 +1,7 @@
 """Pinning the CPU oracle (oracle/rt_oracle.c) — CPU only.
 
-Known answers used (the reference itself is unbuildable here and ships no
-tests):
+Known answers used (the reference ships no tests; the comparison
+with the reference's own source built as host C++ is tests/test_reference_cpu.py):
   * mt19937: the C++ standard's [rand.predef] check (10000th output of a
     default-constructed std::mt19937 is 4123659995) and the first outputs the
     reference produced when run in this container during the survey
