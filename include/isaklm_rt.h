@@ -73,7 +73,10 @@ extern "C" {
  * rt_default_reproject_options, RtReprojectOptions) was added within version
  * 12 in the same way; RT_HAS_REPROJECT is its feature test.  So were the
  * path samplers (rt_sample_paths, rt_sampler_rays, rt_sampler_rays_host,
- * RtSampler); RT_HAS_PATH_SAMPLERS is their feature test.
+ * RtSampler); RT_HAS_PATH_SAMPLERS is their feature test.  So were the
+ * adaptive samplers (rt_sample_paths_adaptive, RtAdaptive;
+ * RT_HAS_ADAPTIVE_SAMPLERS) and the convergence query (rt_convergence,
+ * rt_convergence_host; RT_HAS_CONVERGENCE): new symbols, no struct grew.
  * An integrator checks
  * rt_abi_version() == RT_ABI_VERSION at start-up: a binary built against an
  * older header would otherwise link (C linkage) and mis-pass arguments. */
@@ -825,7 +828,8 @@ int rt_trace_paths(rt_scene_t scene, const float *rays_device, uint32_t *rng_dev
  * is touched).
  *
  * Not covered: AOVs and denoising for the non-pinhole models (rt_sampler_rays(rng = NULL) + rt_trace_rays gives
- * a caller the centre hits), and adaptive sampling: every element takes every sample. */
+ * a caller the centre hits).  rt_sample_paths itself gives every element every sample; the adaptive test is
+ * rt_sample_paths_adaptive's (below). */
 #define RT_HAS_PATH_SAMPLERS 1
 #define RT_SAMPLER_PINHOLE 0
 #define RT_SAMPLER_EQUIRECT 1
@@ -859,6 +863,65 @@ int rt_sample_paths(rt_scene_t scene, const RtSampler *sampler, uint32_t *rng_de
 int rt_sampler_rays(const RtSampler *sampler, uint32_t *rng_device, long long n, float *rays_device, void *stream);
 /* the same arithmetic on host arrays (pixels / points / rng / rays are host pointers), bit for bit */
 int rt_sampler_rays_host(const RtSampler *sampler, uint32_t *rng, long long n, float *rays);
+
+/* ---------------- adaptive samplers (within ABI 12, an addition) ----------------
+ * rt_sample_paths with the renderer's adaptive test (rt/path_tracing.cuh:352-376) in front of every sample:
+ * panoramas, fisheye and orthographic frames and probe sets that stop sampling element by element, as rt_render's
+ * pinhole frames do.  No existing struct grows; with adaptive NULL the call is rt_sample_paths.
+ *
+ * With adaptive given, element e starts from (sum, sum_sq, cnt) = the buffers' contents (accumulate = 1) or
+ * (+0, +0, 0) (accumulate = 0) and runs `samples` passes:
+ *
+ *     if (!adaptive_run(sum, sum_sq, cnt))   the pass is used up: no ray is drawn, no RNG draw is taken
+ *     else (o, d, st) = sampler(e, st); (L, st) = trace_path(o, d, st); sum += L; sum_sq += luminance(L)^2; cnt += 1
+ *
+ * adaptive_run is rt_render's test, operation for operation: cnt < min_samples -> run; else tl = luminance(sum),
+ * mean = tl / cnt, var = (sum_sq - tl*tl / cnt) / (cnt - 1), iw = z * sqrtf(var / cnt) with
+ * z = sqrtf(2) * erfinvf(1 - tolerance) computed on the host, run = iw > mean * tolerance — at min_samples 0 and 1
+ * too, where the variance divides by cnt - 1 <= 0 (0 / 0 is a NaN, which fails the compare: the element stops).  A
+ * skipped pass leaves the state as it was, so every later pass of the call skips too.  At the end radiance,
+ * sq_luminance, sample_count = cnt and rng are written (with accumulate = 1 an element that took no sample is
+ * not stored: the buffers hold those bits).
+ *
+ * THE CONTRACTS.  A PINHOLE sampler with no pixel list on a G_Buffer's four arrays is
+ * rt_render(sample_count = accumulate ? 1 : 0, passes = samples, adaptive = 1, min_samples, tolerance) on that
+ * G_Buffer, bit for bit in all four arrays, in either traversal mode.  For every kind (pixel lists and hemisphere
+ * points included) samples = k equals k host-driven rounds of { the open set A of the current state
+ * (rt_convergence_host); rt_sample_paths(samples = 1, accumulate = 1) on A's gathered rng, radiance, sq, count and
+ * pixel indices or points; scatter back }, bit for bit.
+ *
+ * stats_device keeps RtPathOptions' five words: [1] (paths) is the number of samples actually taken, so
+ * samples * n - paths passes were skipped; a call that adds 0 to [1] found every element converged and adds 0 to
+ * [2] (no ray was traced).
+ *
+ * RT_E_INVALID before any GPU call: what rt_sample_paths checks, and with adaptive given a null
+ * sq_luminance_device or sample_count_device, or min_samples < 0.  tolerance is taken unchecked, as rt_render's. */
+#define RT_HAS_ADAPTIVE_SAMPLERS 1
+typedef struct RtAdaptive { int min_samples; float tolerance; } RtAdaptive;   /* rt_render's MIN_SAMPLES / MAX_TOLERANCE */
+int rt_sample_paths_adaptive(rt_scene_t scene, const RtSampler *sampler, uint32_t *rng_device, long long n,
+                             float *radiance_device, float *sq_luminance_device, int *sample_count_device,
+                             const RtPathOptions *opt, const RtAdaptive *adaptive);
+
+/* ---------------- convergence (within ABI 12, an addition) ----------------
+ * "Is this frame done?": the adaptive test asked of n elements' sums — a G_Buffer's frame_buffer,
+ * squared_luminance and sample_count, or rt_sample_paths' outputs — without sampling anything.  Per element, with
+ * adaptive_run's operations in their order (above):
+ *   open       adaptive_run would run a sample on the next pass;
+ *   stats      4 u64: [0] elements, [1] open elements, [2] elements with count < min_samples, [3] the sum of the
+ *              counts (rt_convergence adds to stats_device, rt_convergence_host writes);
+ *   rel_error  (optional, n floats) +inf for count < 2; 0 where !(iw > 0) (black elements, a variance that rounds
+ *              negative); otherwise the one float division iw / mean.  A diagnostic: open is never derived from it.
+ * rt_convergence (GPU) and rt_convergence_host (CPU) give the same bits.  rt_convergence reads what may be a frame:
+ * like rt_tonemap and rt_denoise it first joins the renders (chained calls' deep-path tails included) on `stream`;
+ * stream NULL = synchronous.  It keeps no workspace.  RT_E_INVALID before any GPU call: a null radiance,
+ * sq_luminance or sample_count pointer, n < 0 or > 2^31 - 1, a misaligned pointer (4 B; stats 8 B),
+ * min_samples < 0.  n == 0: RT_OK without a launch.  tolerance is taken unchecked. */
+#define RT_HAS_CONVERGENCE 1
+int rt_convergence(const float *radiance_device, const float *sq_luminance_device, const int *sample_count_device,
+                   long long n, int min_samples, float tolerance, float *rel_error_device,
+                   unsigned long long *stats_device, void *stream);
+int rt_convergence_host(const float *radiance, const float *sq_luminance, const int *sample_count, long long n,
+                        int min_samples, float tolerance, float *rel_error, unsigned long long stats[4]);
 
 /* draw_frame's colour math (rt/render.cuh:37-59): correct_color(fb/count) ->
  * RGBA8 into a device buffer of width*height*4 bytes, row 0 = bottom. */

@@ -15,13 +15,24 @@
 //                  [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]
 //                  [--reproject-to "PX PY PZ YAW PITCH" [--spp2 N]]
 //                  [--camera-model pinhole|equirect|fisheye|ortho] [--ortho-half-width X]
+//                  [--until-converged] [--error-map PFM]
+// --until-converged asks rt_convergence after every call and stops as soon as
+// the adaptive test (--min-samples, --tolerance) would sample no pixel again —
+// or at --spp, whichever comes first — where the reference's main() keeps
+// launching passes that sample nothing until MAX_SAMPLES.  A converged frame
+// takes no further sample, so the image is the one a full --adaptive 1 --spp N
+// render writes.  It needs the adaptive test: --adaptive 0 with it is a usage
+// error; with --camera-model the frame is rendered by rt_sample_paths_adaptive.
+// It is a usage error with --reproject-to or --shard (a shard sees its rows only).
+// --error-map writes rt_convergence's relative-error map of the shown frame
+// (Pf, --aov's depth layout; inf = fewer than 2 samples).
 // --camera-model renders the frame through rt_sample_paths instead of
 // rt_render: each call draws --passes samples per pixel from the model's
 // sampler (RT_SAMPLER_*; fisheye reads the camera's FOV as the angle across the
 // image circle, ortho takes --ortho-half-width world units, default 2) into
 // the G_Buffer's four arrays, so --checkpoint, --resume and --out work
-// unchanged.  That path never runs the adaptive test and renders whole frames
-// of one camera: with an explicit --adaptive 1, --shard or --reproject-to the
+// unchanged.  That path runs the adaptive test under --until-converged only and renders whole
+// frames of one camera: with an explicit --adaptive 1, --shard or --reproject-to the
 // flag is a usage error, and so is a model other than pinhole with --aov or
 // --denoise (those buffers are the pinhole camera's).
 // --reproject-to moves the camera after the --spp samples (FOV and aperture
@@ -67,7 +78,8 @@ void usage()
             "                 [--kernel mega|wavefront] [--shard G N] [--device D] [--out PNG] [--quiet]\n"
             "                 [--checkpoint FILE] [--resume FILE] [--aov PREFIX] [--denoise]\n"
             "                 [--reproject-to \"PX PY PZ YAW PITCH\" [--spp2 N]]\n"
-            "                 [--camera-model pinhole|equirect|fisheye|ortho] [--ortho-half-width X]\n");
+            "                 [--camera-model pinhole|equirect|fisheye|ortho] [--ortho-half-width X]\n"
+            "                 [--until-converged] [--error-map PFM]\n");
 }
 
 // PFM: "PF" (3 channels) or "Pf" (1), width height, a negative scale = little-endian, rows bottom to top
@@ -166,7 +178,8 @@ int main(int argc, char **argv)
     int device = 0, shard_id = 0, num_shards = 1, kernel = RT_KERNEL_WAVEFRONT;
     int camera_model = -1; // RT_SAMPLER_*; -1: rt_render
     float tolerance = 0.05f, ortho_half_width = 2.0f;
-    bool quiet = false, denoise = false, adaptive_given = false, shard_given = false;
+    bool quiet = false, denoise = false, adaptive_given = false, shard_given = false, until_converged = false;
+    std::string error_map;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&](void) -> const char * {
@@ -203,6 +216,8 @@ int main(int argc, char **argv)
                            : m == "fisheye" ? RT_SAMPLER_FISHEYE : m == "ortho" ? RT_SAMPLER_ORTHO : -2;
         }
         else if (a == "--ortho-half-width") ortho_half_width = (float)atof(next());
+        else if (a == "--until-converged") until_converged = true;
+        else if (a == "--error-map") error_map = next();
         else {
             usage();
             return 2;
@@ -217,6 +232,15 @@ int main(int argc, char **argv)
     if (camera_model == -2 ||
         (camera_model >= 0 && ((adaptive_given && adaptive != 0) || shard_given || !reproject_to.empty())) ||
         (camera_model > RT_SAMPLER_PINHOLE && (!aov.empty() || denoise))) {
+        usage();
+        return 2;
+    }
+    // "is the frame done" is the adaptive test's question, asked of a whole frame of one camera
+    if (until_converged && ((camera_model < 0 && adaptive == 0) || shard_given || !reproject_to.empty() || min_samples < 0)) {
+        usage();
+        return 2;
+    }
+    if (!error_map.empty() && min_samples < 0) {
         usage();
         return 2;
     }
@@ -270,7 +294,13 @@ int main(int argc, char **argv)
         if (rt_gbuffer_load(resume.c_str(), g_buffer, width, height, &sample_count) != RT_OK) return fail("resume");
         if (!quiet) printf("resumed at %d samples per pixel\n", sample_count);
     }
-    while (sample_count < spp) {
+    const long long n_pixels = (long long)width * height;
+    unsigned long long *conv_stats = nullptr; // --until-converged: rt_convergence's four words
+    unsigned long long conv[4] = {0, 0, 0, 0};
+    bool converged = false;
+    if (until_converged && rt_device_alloc((void **)&conv_stats, sizeof conv) != RT_OK) return fail("convergence stats");
+    const RtAdaptive adaptive_test = {min_samples, tolerance};
+    while (sample_count < spp && !converged) {
         opt.passes = passes < spp - sample_count ? passes : spp - sample_count;
         if (camera_model >= 0) {
             const RtSampler sampler = {camera_model, width, height, camera, ortho_half_width, nullptr, nullptr};
@@ -279,18 +309,37 @@ int main(int argc, char **argv)
             po.samples = opt.passes;
             po.max_depth = max_depth;
             po.accumulate = sample_count > 0;
-            if (rt_sample_paths(prepared, &sampler, g_buffer.random_numbers, (long long)width * height,
-                                (float *)g_buffer.frame_buffer, g_buffer.squared_luminance, g_buffer.sample_count,
-                                &po) != RT_OK)
+            if (rt_sample_paths_adaptive(prepared, &sampler, g_buffer.random_numbers, n_pixels,
+                                         (float *)g_buffer.frame_buffer, g_buffer.squared_luminance,
+                                         g_buffer.sample_count, &po, until_converged ? &adaptive_test : nullptr) != RT_OK)
                 return fail("sample_paths");
         } else if (rt_render(prepared, g_buffer, camera, sample_count, &opt) != RT_OK) return fail("render");
         sample_count += opt.passes;
         if (!checkpoint.empty() && rt_gbuffer_save(g_buffer, width, height, sample_count, checkpoint.c_str()) != RT_OK)
             return fail("checkpoint");
         if (!quiet) printf("samples per pixel: %d\n", sample_count);
+        if (until_converged) { // (rt_convergence joins the renders first)
+            if (rt_memset(conv_stats, 0, sizeof conv) != RT_OK ||
+                rt_convergence((const float *)g_buffer.frame_buffer, g_buffer.squared_luminance, g_buffer.sample_count,
+                               n_pixels, min_samples, tolerance, nullptr, conv_stats, nullptr) != RT_OK ||
+                rt_download(conv, conv_stats, sizeof conv) != RT_OK)
+                return fail("convergence");
+            converged = conv[1] == 0;
+        }
     }
     if (rt_synchronize() != RT_OK) return fail("synchronize");
     const double render_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    // the samples the rate line counts: the ones actually taken where the driver knows them
+    double samples_taken = (double)n_pixels * spp;
+    if (until_converged && conv[0]) { // (no call ran if --resume already was at --spp: nothing to report then)
+        samples_taken = (double)conv[3];
+        if (converged)
+            printf("converged after %d passes: %llu samples (mean %.2f per pixel)\n", sample_count, conv[3],
+                   (double)conv[3] / (double)n_pixels);
+        else
+            printf("not converged: %llu pixels open\n", conv[1]);
+    }
+    if (conv_stats) rt_free(conv_stats);
 
     // --reproject-to: the camera moves; where main() resets (rt/main.cu:114-155) the frame is carried over
     G_Buffer moved = {nullptr, nullptr, nullptr, nullptr};
@@ -325,8 +374,26 @@ int main(int argc, char **argv)
     }
     const G_Buffer shown = moved.frame_buffer ? moved : g_buffer;
     if (rt_save_render(shown, width, height, out.c_str()) != RT_OK) return fail("save_render");
-    printf("rendered %dx%d x %d spp in %.3f s (%.2f Msamples/s nominal; scene setup %.2f s) -> %s\n", width, height,
-           spp, render_s, (double)width * height * spp / render_s / 1e6, setup_s, out.c_str());
+    if (until_converged)
+        printf("rendered %dx%d x %d passes in %.3f s (%.2f Msamples/s taken; scene setup %.2f s) -> %s\n", width, height,
+               sample_count, render_s, samples_taken / render_s / 1e6, setup_s, out.c_str());
+    else
+        printf("rendered %dx%d x %d spp in %.3f s (%.2f Msamples/s nominal; scene setup %.2f s) -> %s\n", width,
+               height, spp, render_s, samples_taken / render_s / 1e6, setup_s, out.c_str());
+    if (!error_map.empty()) {
+        float *err = nullptr;
+        std::vector<float> host((size_t)n_pixels);
+        if (rt_device_alloc((void **)&err, (size_t)n_pixels * 4) != RT_OK) return fail("error map");
+        if (rt_convergence((const float *)shown.frame_buffer, shown.squared_luminance, shown.sample_count, n_pixels,
+                           min_samples, tolerance, err, nullptr, nullptr) != RT_OK ||
+            rt_download(host.data(), err, (size_t)n_pixels * 4) != RT_OK)
+            return fail("error map");
+        rt_free(err);
+        if (!write_pfm(error_map, host.data(), width, height, 1)) {
+            fprintf(stderr, "rt_render: cannot write %s\n", error_map.c_str());
+            return 1;
+        }
+    }
     if (denoise) {
         if (!aov_buffers.depth && render_aovs(prepared, camera, width, height, &aov_buffers) != 0) return 1;
         const std::string path = denoised_path(out);

@@ -22,8 +22,9 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 HOST_SOURCES = ["host/mesh_loading.cpp", "host/kd_build.cpp", "host/scene_prepare.cpp", "host/misc.cpp", "host/image_decode.cpp",
                 "host/scenes.cpp", "host/bvh_build.cpp", "host/denoise_host.cpp", "host/reproject_host.cpp",
-                "host/sampler_host.cpp"]
-HIP_SOURCES = ["path_kernel.hip", "wavefront.hip", "abi.hip", "shards.hip", "query.hip", "denoise.hip", "reproject.hip"]
+                "host/sampler_host.cpp", "host/convergence_host.cpp"]
+HIP_SOURCES = ["path_kernel.hip", "wavefront.hip", "abi.hip", "shards.hip", "query.hip", "denoise.hip", "reproject.hip",
+               "convergence.hip"]
 # every header under csrc/ (a header missing here would not trigger a rebuild)
 HEADERS = sorted(os.path.relpath(f, os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc"))
                  for f in glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "**", "*.h"),

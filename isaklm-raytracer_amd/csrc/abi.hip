@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "camera_math.h"
+#include "convergence_math.h"
 #include "denoise_math.h"
 #include "host/rt_host.h"
 #include "reproject_math.h"
@@ -989,42 +990,68 @@ int rt_trace_paths(rt_scene_t scene, const float *rays, uint32_t *rng, long long
                        stream);
 }
 
-// rt_trace_paths for rays a sampler draws on the device (sampler_math.h)
-int rt_sample_paths(rt_scene_t scene, const RtSampler *sampler, uint32_t *rng, long long n, float *radiance,
-                    float *sq_luminance, int *sample_count, const RtPathOptions *opt)
+// rt_trace_paths for rays a sampler draws on the device (sampler_math.h); adaptive: NULL, or the adaptive test's
+// constants (rt_render's MIN_SAMPLES / MAX_TOLERANCE) — who: the entry point's name
+static int sample_paths(const char *who, rt_scene_t scene, const RtSampler *sampler, uint32_t *rng, long long n,
+                        float *radiance, float *sq_luminance, int *sample_count, const RtPathOptions *opt,
+                        const RtAdaptive *adaptive)
 {
     RtPathOptions o;
     if (opt) o = *opt; else rt_default_path_options(&o);
-    if (!scene) { rt_set_error("rt_sample_paths: null scene"); return RT_E_INVALID; }
-    if (!rng || !radiance) { rt_set_error("rt_sample_paths: null rng or radiance"); return RT_E_INVALID; }
-    if (!count_ok("rt_sample_paths", n)) return RT_E_INVALID;
+    if (!scene) { rt_set_error("%s: null scene", who); return RT_E_INVALID; }
+    if (!rng || !radiance) { rt_set_error("%s: null rng or radiance", who); return RT_E_INVALID; }
+    if (!count_ok(who, n)) return RT_E_INVALID;
     if (misaligned(rng, 4) || misaligned(radiance, 4) || misaligned(sq_luminance, 4) || misaligned(sample_count, 4) ||
         misaligned(o.stats_device, 8)) {
-        rt_set_error("rt_sample_paths: misaligned pointer (stats_device 8 B, rng, radiance, sq_luminance and "
-                     "sample_count 4 B)");
+        rt_set_error("%s: misaligned pointer (stats_device 8 B, rng, radiance, sq_luminance and "
+                     "sample_count 4 B)", who);
         return RT_E_INVALID;
     }
     if (o.samples < 0 || o.samples > (1 << 20) || o.max_depth < 0 || o.max_depth > RT_WATCHDOG_BOUNCES ||
         (o.accumulate != 0 && o.accumulate != 1)) {
-        rt_set_error("rt_sample_paths: samples %d (0 .. 2^20), max_depth %d (0 .. 2^24 - 1) or accumulate %d (0 / 1)",
+        rt_set_error("%s: samples %d (0 .. 2^20), max_depth %d (0 .. 2^24 - 1) or accumulate %d (0 / 1)", who,
                      o.samples, o.max_depth, o.accumulate);
         return RT_E_INVALID;
     }
-    if (!traversal_ok("rt_sample_paths", o.traversal)) return RT_E_INVALID;
+    if (!traversal_ok(who, o.traversal)) return RT_E_INVALID;
     RtDevSampler smp;
     if (const char *why = rt_sampler_resolve(sampler, n, &smp)) {
-        rt_set_error("rt_sample_paths: %s", why);
+        rt_set_error("%s: %s", who, why);
+        return RT_E_INVALID;
+    }
+    if (adaptive && (!sq_luminance || !sample_count)) {
+        rt_set_error("%s: the adaptive test needs sq_luminance and sample_count", who);
+        return RT_E_INVALID;
+    }
+    if (adaptive && adaptive->min_samples < 0) {
+        rt_set_error("%s: min_samples %d < 0", who, adaptive->min_samples);
         return RT_E_INVALID;
     }
     if (n == 0) return RT_OK;
-    if (!stack_depth_ok("rt_sample_paths", scene)) return RT_E_UNSUPPORTED;
+    if (!stack_depth_ok(who, scene)) return RT_E_UNSUPPORTED;
     rt_register_shutdown();
     hipStream_t stream = (hipStream_t)o.stream;
-    return launch_done("rt_sample_paths",
+    RtCvParams test;
+    if (adaptive) test = rt_cv_params(adaptive->min_samples, adaptive->tolerance); // (the tolerance unchecked, as rt_render's)
+    return launch_done(who,
                        rt_launch_sample_paths(scene->dev, smp, rng, n, radiance, sq_luminance, sample_count,
                                               o.samples ? o.samples : 1, o.max_depth, o.accumulate, o.traversal,
-                                              o.stats_device, stream),
+                                              o.stats_device, stream, adaptive ? &test : nullptr),
                        stream);
+}
+
+int rt_sample_paths(rt_scene_t scene, const RtSampler *sampler, uint32_t *rng, long long n, float *radiance,
+                    float *sq_luminance, int *sample_count, const RtPathOptions *opt)
+{
+    return sample_paths("rt_sample_paths", scene, sampler, rng, n, radiance, sq_luminance, sample_count, opt, nullptr);
+}
+
+int rt_sample_paths_adaptive(rt_scene_t scene, const RtSampler *sampler, uint32_t *rng, long long n, float *radiance,
+                             float *sq_luminance, int *sample_count, const RtPathOptions *opt,
+                             const RtAdaptive *adaptive)
+{
+    return sample_paths(adaptive ? "rt_sample_paths_adaptive" : "rt_sample_paths", scene, sampler, rng, n, radiance,
+                        sq_luminance, sample_count, opt, adaptive);
 }
 
 int rt_sampler_rays(const RtSampler *sampler, uint32_t *rng, long long n, float *rays, void *stream)
@@ -1099,6 +1126,24 @@ int rt_tonemap(G_Buffer g, uint8_t *rgba, int w, int h, void *stream)
     if (jr != RT_OK) return jr;
     return launch_done("rt_tonemap",
                        rt_launch_tonemap(g.frame_buffer, g.sample_count, (RtUChar4 *)rgba, w * h, (hipStream_t)stream),
+                       (hipStream_t)stream);
+}
+
+// ---------------- convergence (convergence.hip; rt_convergence_host: host/convergence_host.cpp) ----------------
+int rt_convergence(const float *radiance, const float *sq_luminance, const int *sample_count, long long n,
+                   int min_samples, float tolerance, float *rel_error, unsigned long long *stats, void *stream)
+{
+    if (const char *why = rt_cv_check(radiance, sq_luminance, sample_count, n, min_samples, rel_error)) {
+        rt_set_error("rt_convergence: %s", why);
+        return RT_E_INVALID;
+    }
+    if (misaligned(stats, 8)) { rt_set_error("rt_convergence: stats_device is not 8-byte aligned"); return RT_E_INVALID; }
+    if (n == 0) return RT_OK;
+    const int jr = join_status(stream, "rt_convergence"); // chained renders' deep-path tails first, as rt_tonemap
+    if (jr != RT_OK) return jr;
+    return launch_done("rt_convergence",
+                       rt_launch_convergence(radiance, sq_luminance, sample_count, n, rt_cv_params(min_samples, tolerance),
+                                             rel_error, stats, (hipStream_t)stream),
                        (hipStream_t)stream);
 }
 

@@ -16,6 +16,7 @@
 // and a third that runs the renderer's whole path loop on the caller's rays:
 //   rt_trace_paths  rays + RNG states        -> summed radiance per ray
 //   rt_sample_paths a sampler + RNG states   -> summed radiance per element
+//   rt_sample_paths_adaptive  the same, the renderer's adaptive test before every sample
 //
 // One ray per lane; the lanes of a wave take their next rays together from a
 // global counter (one wave-aggregated atomic per round).  The traversal stack
@@ -35,6 +36,7 @@
 
 #include "bvh_trace.h"
 #include "camera_math.h"
+#include "convergence_math.h"
 #include "path_event.h"
 #include "rt_kernels.h"
 #include "rt_launch.h"
@@ -358,12 +360,25 @@ __global__ void __launch_bounds__(RQ_BLOCK, RQ_WAVES)
 // from p.rng where that restart stands — in the iteration the lane's previous
 // path ended in, like any other regeneration — and keeps the element's
 // sample count.
-template <typename SRC>
+//
+// ADAPT (rt_sample_paths_adaptive; SamplerRays with sq_out and src.count
+// given): the lane keeps its element's sample count, and the adaptive test
+// (rt_kernels.h adaptive_run, rt_render's own, on min_samples / tolerance /
+// z_const) stands at the regeneration point, before each of the element's
+// `samples` passes.  A pass the test refuses draws nothing and leaves the sums
+// as they were, so every later pass of the call would be refused too: the
+// element is done.  It stores its records and the lane takes the next index
+// within the same iteration — a wave of converged elements spends no ray
+// query on them.  With `accumulate` an element that took no sample is not
+// stored: its records would be rewritten with the bits they hold.
+template <typename SRC, bool ADAPT>
 __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
     rt_path_query_kernel(RtDevScene sc, SRC src, uint32_t *rng_io, float *radiance, float *sq_out, uint32_t n,
                          int samples, int limit, int accumulate, int kd_only, uint32_t *fetch,
-                         unsigned long long *stats, uint2 *spill, int spill_threads)
+                         unsigned long long *stats, uint2 *spill, int spill_threads, int min_samples, float tolerance,
+                         float z_const)
 {
+    static_assert(!ADAPT || SRC::per_sample, "the adaptive test needs the sampler's per-element count");
     __shared__ uint32_t s_node[PQ_LDS * RQ_BLOCK];
     __shared__ float s_entry[PQ_LDS * RQ_BLOCK];
     const int tid = threadIdx.x;
@@ -380,10 +395,60 @@ __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
     Vec3D sum = rt_v3(0, 0, 0);
     float sum_sq = 0.0f;
     PathState p; // (p.rng: the ray's RNG state, carried from sample to sample)
+    int cnt = 0;        // ADAPT: the element's sample count
+    bool taken = false; // ADAPT: the element took a sample in this call
+    RtDevFrame afr;     // ADAPT: the fields adaptive_run reads
+    if constexpr (ADAPT) {
+        afr.adaptive = 1;
+        afr.min_samples = min_samples;
+        afr.tolerance = tolerance;
+        afr.z_const = z_const;
+    }
 
     while (true) {
         if (!have_path) {
-            if (samples_left == 0) {
+            if constexpr (ADAPT) {
+                bool leave = false;
+                while (true) { // one round per element that the test stops before its first sample of the call
+                    if (samples_left == 0) {
+                        if (have_ray && (taken || !accumulate)) { // the finished element's records
+                            float *r = radiance + 3 * (size_t)e;
+                            r[0] = sum.x;
+                            r[1] = sum.y;
+                            r[2] = sum.z;
+                            sq_out[e] = sum_sq;
+                            rng_io[e] = p.rng;
+                            src.count[e] = cnt;
+                        }
+                        have_ray = false;
+                        const uint32_t next = wave_next_index(fetch, lane); // for the lanes that are here
+                        if (next >= n) {
+                            leave = true;
+                            break;
+                        }
+                        e = next;
+                        p.rng = rng_io[e];
+                        sum = rt_v3(0.0f, 0.0f, 0.0f);
+                        sum_sq = 0.0f;
+                        cnt = 0;
+                        if (accumulate) {
+                            const float *r = radiance + 3 * (size_t)e;
+                            sum = rt_v3(r[0], r[1], r[2]);
+                            sum_sq = sq_out[e];
+                            cnt = src.count[e];
+                        }
+                        have_ray = true;
+                        taken = false;
+                        samples_left = samples;
+                        ++n_rays;
+                    }
+                    if (adaptive_run(afr, sum, sum_sq, cnt)) break;
+                    samples_left = 0; // this pass is used up, and so is every later one of the call: the state stays
+                }
+                if (leave) break;
+                taken = true;
+            } else if (samples_left == 0) { // (its own block on purpose: shared with ADAPT's loop, these
+                                            // instantiations' register allocation changed)
                 if (have_ray) { // the finished ray's records
                     float *r = radiance + 3 * (size_t)e;
                     r[0] = sum.x;
@@ -449,6 +514,7 @@ __global__ void __launch_bounds__(RQ_BLOCK, PQ_WAVES)
         if (finish) { // accumulation (:322-324)
             sum = sum + p.L;
             sum_sq = sum_sq + rt_square(rt_luminance(p.L));
+            if constexpr (ADAPT) ++cnt;
             max_len = (uint32_t)p.depth > max_len ? (uint32_t)p.depth : max_len;
             have_path = false;
         }
@@ -604,18 +670,20 @@ int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tma
 }
 
 namespace {
-template <typename SRC>
+// (ad: the adaptive test's constants, ADAPT only)
+template <typename SRC, bool ADAPT = false>
 int launch_path_query(const RtDevScene &sc, const SRC &src, uint32_t *rng, long long n, float *radiance, float *sq,
                       int samples, int max_depth, int accumulate, int traversal, unsigned long long *stats,
-                      hipStream_t stream)
+                      hipStream_t stream, const RtCvParams &ad = RtCvParams{0, 0.0f, 0.0f})
 {
     static_assert(PQ_WAVES <= RQ_WAVES && PQ_LDS >= RQ_LDS, "rt_path_query_kernel within the shared spill area");
     std::lock_guard<std::mutex> g(g_query.mu);
     QueryWorkspace *w = query_workspace(stream);
     if (!w) return -1;
-    hipLaunchKernelGGL(rt_path_query_kernel<SRC>, dim3(query_grid(*w, n, PQ_WAVES)), dim3(RQ_BLOCK), 0, stream, sc, src, rng,
-                       radiance, sq, (uint32_t)n, samples, max_depth > 0 ? max_depth : RT_WATCHDOG_BOUNCES, accumulate,
-                       (int)query_kd_only(sc, traversal), w->fetch, stats, w->spill, (int)w->spill_threads);
+    hipLaunchKernelGGL((rt_path_query_kernel<SRC, ADAPT>), dim3(query_grid(*w, n, PQ_WAVES)), dim3(RQ_BLOCK), 0, stream, sc,
+                       src, rng, radiance, sq, (uint32_t)n, samples, max_depth > 0 ? max_depth : RT_WATCHDOG_BOUNCES,
+                       accumulate, (int)query_kd_only(sc, traversal), w->fetch, stats, w->spill, (int)w->spill_threads,
+                       ad.min_samples, ad.tolerance, ad.z_const);
     return w->serial.record(stream) ? 0 : -1;
 }
 } // namespace
@@ -630,8 +698,11 @@ int rt_launch_trace_paths(const RtDevScene &sc, const float *rays, uint32_t *rng
 
 int rt_launch_sample_paths(const RtDevScene &sc, const RtDevSampler &smp, uint32_t *rng, long long n, float *radiance,
                            float *sq, int *count, int samples, int max_depth, int accumulate, int traversal,
-                           unsigned long long *stats, hipStream_t stream)
+                           unsigned long long *stats, hipStream_t stream, const RtCvParams *adaptive)
 {
+    if (adaptive) // (sq and count are given: abi.hip checks)
+        return launch_path_query<SamplerRays, true>(sc, SamplerRays{smp, count}, rng, n, radiance, sq, samples,
+                                                    max_depth, accumulate, traversal, stats, stream, *adaptive);
     return launch_path_query(sc, SamplerRays{smp, count}, rng, n, radiance, sq, samples, max_depth, accumulate,
                              traversal, stats, stream);
 }

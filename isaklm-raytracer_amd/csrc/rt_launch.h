@@ -10,6 +10,7 @@ struct RtDnParams; // denoise_math.h
 struct RtRpFrame;  // reproject_math.h
 struct RtRpParams;
 struct RtDevSampler; // sampler_math.h
+struct RtCvParams;   // convergence_math.h
 
 // path_kernel.hip: the megakernel and rt_tonemap
 int rt_launch_path(const RtDevScene &sc, const RtDevFrame &fr, const RtDevCamera &cam, int stack_depth,
@@ -37,9 +38,10 @@ int rt_launch_occluded(const RtDevScene &sc, const float *rays, const float *tma
 int rt_launch_trace_paths(const RtDevScene &sc, const float *rays, uint32_t *rng, long long n, float *radiance, float *sq,
                           int samples, int max_depth, int accumulate, int traversal, unsigned long long *stats,
                           hipStream_t stream);
+// (adaptive: NULL = every element takes every sample; else rt_sample_paths_adaptive's test, sq and count given)
 int rt_launch_sample_paths(const RtDevScene &sc, const RtDevSampler &smp, uint32_t *rng, long long n, float *radiance,
                            float *sq, int *count, int samples, int max_depth, int accumulate, int traversal,
-                           unsigned long long *stats, hipStream_t stream);
+                           unsigned long long *stats, hipStream_t stream, const RtCvParams *adaptive);
 int rt_launch_sampler_rays(const RtDevSampler &smp, uint32_t *rng, long long n, float *rays, hipStream_t stream);
 void rt_query_shutdown();
 
@@ -55,6 +57,10 @@ int rt_launch_reproject(const RtRpFrame &src, const RtDevCamera &src_cam, const 
                         const float *dst_normal, const int *dst_triangle, const RtDevCamera &dst_cam, int width,
                         int height, const RtRpParams &prm, Vec3D *fb_out, float *sq_out, int *count_out,
                         unsigned long long *stats, hipStream_t stream);
+
+// convergence.hip
+int rt_launch_convergence(const float *radiance, const float *sq, const int *count, long long n, const RtCvParams &prm,
+                          float *rel_error, unsigned long long *stats, hipStream_t stream);
 
 // abi.hip: rt_shutdown at exit, before the HIP runtime's finalisers
 void rt_register_shutdown();

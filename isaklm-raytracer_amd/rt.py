@@ -82,6 +82,10 @@ class RtSampler(ctypes.Structure):
                 ("points_device", ctypes.c_void_p)]
 
 
+class RtAdaptive(ctypes.Structure):
+    _fields_ = [("min_samples", ctypes.c_int), ("tolerance", ctypes.c_float)]
+
+
 class RtAovBuffers(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
                 ("triangle", ctypes.c_void_p)]
@@ -262,6 +266,12 @@ def lib():
                                           ctypes.POINTER(RtPathOptions)]
             L.rt_sampler_rays.argtypes = [ctypes.POINTER(RtSampler), vp, ctypes.c_longlong, vp, vp]
             L.rt_sampler_rays_host.argtypes = [ctypes.POINTER(RtSampler), vp, ctypes.c_longlong, vp]
+        if hasattr(L, "rt_sample_paths_adaptive"):  # (added within ABI 12: an earlier ABI-12 library lacks it)
+            L.rt_sample_paths_adaptive.argtypes = [vp, ctypes.POINTER(RtSampler), vp, ctypes.c_longlong, vp, vp, vp,
+                                                   ctypes.POINTER(RtPathOptions), ctypes.POINTER(RtAdaptive)]
+        if hasattr(L, "rt_convergence"):  # (added within ABI 12: an earlier ABI-12 library lacks it)
+            L.rt_convergence.argtypes = [vp, vp, vp, ctypes.c_longlong, i, ctypes.c_float, vp, vp, vp]
+            L.rt_convergence_host.argtypes = [vp, vp, vp, ctypes.c_longlong, i, ctypes.c_float, vp, vp]
         L.rt_render_aov.argtypes = [vp, Camera, i, i, ctypes.POINTER(RtAovBuffers), ctypes.POINTER(RtQueryOptions)]
         L.rt_default_denoise_options.argtypes = [ctypes.POINTER(RtDenoiseOptions)]
         L.rt_default_denoise_options.restype = None
@@ -753,13 +763,21 @@ class Sampler:
 
 def sample_paths_device(dscene, sampler, rng_ptr, n, radiance_ptr, sq_ptr=None, count_ptr=None, samples=1, max_depth=0,
                         accumulate=False, traversal=None, stream=None, stats_ptr=None, pixels_ptr=None,
-                        points_ptr=None):
+                        points_ptr=None, adaptive=None):
     """rt_sample_paths on device memory: `sampler` a Sampler (its arrays are not used: pixels_ptr / points_ptr
     are the device pointers to them); integer device pointers to n uint32 RNG states (read and written), n x 3
     float32 radiance sums, optionally n float32 sums of squared luminance and n int32 sample counts — a
-    G_Buffer's four arrays, for a whole frame; stream: an integer hipStream_t — the call is then only enqueued."""
+    G_Buffer's four arrays, for a whole frame; stream: an integer hipStream_t — the call is then only enqueued.
+    adaptive=(min_samples, tolerance): rt_sample_paths_adaptive — the renderer's adaptive test before every
+    sample (sq_ptr and count_ptr are then required)."""
     o = path_options(samples, max_depth, accumulate, traversal, stream, _int_ptr(stats_ptr))
     smp = sampler.struct(pixels_ptr, points_ptr)
+    if adaptive is not None:
+        ad = RtAdaptive(int(adaptive[0]), float(adaptive[1]))
+        check(lib().rt_sample_paths_adaptive(dscene.prepared, ctypes.byref(smp), _int_ptr(rng_ptr), int(n),
+                                             _int_ptr(radiance_ptr), _int_ptr(sq_ptr), _int_ptr(count_ptr),
+                                             ctypes.byref(o), ctypes.byref(ad)))
+        return
     check(lib().rt_sample_paths(dscene.prepared, ctypes.byref(smp), _int_ptr(rng_ptr), int(n), _int_ptr(radiance_ptr),
                                 _int_ptr(sq_ptr), _int_ptr(count_ptr), ctypes.byref(o)))
 
@@ -793,12 +811,19 @@ class _SamplerArrays:
 
 
 def sample_paths(dscene, sampler, rng, samples=1, max_depth=0, traversal=None, stream=None, stats=False,
-                 radiance=None, sq=None, count=None):
+                 radiance=None, sq=None, count=None, adaptive=None):
     """Path-traced radiance of `samples` rays per element drawn by `sampler` (a Sampler) on the device from the
     (n,) uint32 RNG states `rng`.  Returns (radiance (n, 3) float32, sq (n,) float32, rng_out (n,) uint32): the
     SUMS over the samples, as trace_paths; with count=True also the (n,) int32 sample counts; with stats=True
     also a dict of the call's counts (PATH_STATS).  Passing `radiance` (with `sq`, and `count` as an int32 array)
-    of an earlier call accumulates onto them (they are not modified)."""
+    of an earlier call accumulates onto them (they are not modified).  adaptive=(min_samples, tolerance): the
+    renderer's adaptive test before every sample (rt_sample_paths_adaptive) — an element takes at most `samples`
+    samples; the counts are then always returned (count=True is implied), and accumulating needs all three arrays."""
+    if adaptive is not None:
+        if radiance is not None and (sq is None or count is None or isinstance(count, bool)):
+            raise ValueError("adaptive accumulation needs the radiance, sq and count arrays of the earlier call")
+        if count is None or count is False:
+            count = True
     n = sampler.n
     rng = np.asarray(rng)
     if rng.dtype != np.uint32 or rng.shape != (n,):
@@ -832,7 +857,7 @@ def sample_paths(dscene, sampler, rng, samples=1, max_depth=0, traversal=None, s
         if stats:
             check(L.rt_memset(d_st, 0, st.nbytes))
         sample_paths_device(dscene, sampler, d_rng, n, d_rad, d_sq, d_cnt if want_count else None, samples, max_depth,
-                            accumulate, traversal, stream, d_st if stats else None, d_pix, d_pts)
+                            accumulate, traversal, stream, d_st if stats else None, d_pix, d_pts, adaptive)
         _synchronize_stream(stream)
         if n:
             check(L.rt_download(_ptr(rad), d_rad, rad.nbytes))
@@ -844,6 +869,62 @@ def sample_paths(dscene, sampler, rng, samples=1, max_depth=0, traversal=None, s
             check(L.rt_download(_ptr(st), d_st, st.nbytes))
     out = (rad, sqv, rng) + ((cnt,) if want_count else ())
     return out + (dict(zip(PATH_STATS, (int(v) for v in st))),) if stats else out
+
+
+CONVERGENCE_STATS = ("elements", "open", "below_min", "samples")  # rt_convergence's stats [0..3]
+
+
+def convergence_device(radiance_ptr, sq_ptr, count_ptr, n, min_samples, tolerance, rel_error_ptr=None, stats_ptr=None,
+                       stream=None):
+    """rt_convergence on device memory: integer device pointers to n x 3 float32 radiance sums, n float32 sums of
+    squared luminance and n int32 sample counts (a G_Buffer's arrays, or sample_paths' outputs); optionally n
+    float32 for the relative-error map and 4 u64 the call adds CONVERGENCE_STATS to."""
+    check(lib().rt_convergence(_int_ptr(radiance_ptr), _int_ptr(sq_ptr), _int_ptr(count_ptr), int(n), int(min_samples),
+                               float(tolerance), _int_ptr(rel_error_ptr), _int_ptr(stats_ptr), stream))
+
+
+def _convergence_arrays(radiance, sq, count):
+    radiance = np.ascontiguousarray(radiance, dtype=np.float32)
+    sq = np.ascontiguousarray(sq, dtype=np.float32).reshape(-1)
+    count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+    n = len(count)
+    if radiance.size != 3 * n or sq.size != n:
+        raise ValueError("radiance must hold n x 3, sq and count n values")
+    return radiance.reshape(n, 3), sq, count, n
+
+
+def convergence(radiance, sq, count, min_samples, tolerance, rel_error=False):
+    """rt_convergence on numpy arrays (uploaded for the call): a dict of CONVERGENCE_STATS — `open` is the number
+    of elements the adaptive test would sample on the next pass, 0 = converged; with rel_error=True also the (n,)
+    float32 relative-error map."""
+    radiance, sq, count, n = _convergence_arrays(radiance, sq, count)
+    L = lib()
+    st = np.zeros(4, dtype=np.uint64)
+    err = np.zeros(n, dtype=np.float32)
+    with _DeviceBytes(radiance.nbytes) as d_rad, _DeviceBytes(sq.nbytes) as d_sq, _DeviceBytes(count.nbytes) as d_cnt, \
+            _DeviceBytes(err.nbytes) as d_err, _DeviceBytes(st.nbytes) as d_st:
+        if n:
+            check(L.rt_upload(d_rad, _ptr(radiance), radiance.nbytes))
+            check(L.rt_upload(d_sq, _ptr(sq), sq.nbytes))
+            check(L.rt_upload(d_cnt, _ptr(count), count.nbytes))
+        check(L.rt_memset(d_st, 0, st.nbytes))
+        convergence_device(d_rad, d_sq, d_cnt, n, min_samples, tolerance, d_err if rel_error and n else None, d_st)
+        check(L.rt_download(_ptr(st), d_st, st.nbytes))
+        if rel_error and n:
+            check(L.rt_download(_ptr(err), d_err, err.nbytes))
+    stats = dict(zip(CONVERGENCE_STATS, (int(v) for v in st)))
+    return (stats, err) if rel_error else stats
+
+
+def convergence_host(radiance, sq, count, min_samples, tolerance, rel_error=False):
+    """rt_convergence_host: convergence computed on the host, bit for bit (no GPU is touched)."""
+    radiance, sq, count, n = _convergence_arrays(radiance, sq, count)
+    st = np.zeros(4, dtype=np.uint64)
+    err = np.zeros(max(n, 1), dtype=np.float32)
+    check(lib().rt_convergence_host(_ptr(radiance), _ptr(sq), _ptr(count), n, int(min_samples), float(tolerance),
+                                    _ptr(err) if rel_error else None, _ptr(st)))
+    stats = dict(zip(CONVERGENCE_STATS, (int(v) for v in st)))
+    return (stats, err[:n]) if rel_error else stats
 
 
 def _sampler_rng(sampler, rng):
