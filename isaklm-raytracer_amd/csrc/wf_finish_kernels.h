@@ -75,12 +75,12 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
     // (fresh: the listed heavy pixels first, then the tiles)
     const uint32_t n_heavy = st.fresh && st.heavy_list ? *st.heavy_n : 0u;
     const uint32_t n = st.fresh ? n_heavy + st.fresh_n : st.counts[6 + q];
-    uint32_t *fetch = st.counts + 4;
     const int limit = fr.max_depth > 0 ? fr.max_depth : RT_WATCHDOG_BOUNCES;
     const int lane = __lane_id();
-    unsigned long long *const ret_word = reinterpret_cast<unsigned long long *>(st.ret_ctr);
-    uint32_t *const ret_claimed = st.ret_ctr + 2;
+    // (RT_COLD_ARGS, wf_state.h: the loop reads st.fresh, long_return, linger, long_depth, chk, chk_mask and the stack's
+    // spill base from registers; every other field of the state where it is used, through WF_COLD)
     if (lane == 0) {
+        unsigned long long *const ret_word = reinterpret_cast<unsigned long long *>(st.ret_ctr);
         // the call's finisher has started: from here wf_long waits for its producers (WF_FIN_STARTED)
         if (st.fin_live && !(__hip_atomic_load(st.fin_live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & WF_FIN_STARTED))
             __hip_atomic_fetch_or(st.fin_live, WF_FIN_STARTED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -127,22 +127,24 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
         // kernel boundary orders this lane's stores before its loads.)
         while (st.fresh && __any(rel)) {
             if (rel) {
+                WfCold &cs = WF_COLD(st);
                 uint32_t x = RT_PX_BUSY;
-                if (__hip_atomic_compare_exchange_strong(st.pxo + p.slot, &x, 0u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                if (__hip_atomic_compare_exchange_strong(cs.pxo + p.slot, &x, 0u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                                          __HIP_MEMORY_SCOPE_AGENT)) {
                     rel = false;
                 } else {
-                    x = __hip_atomic_exchange(st.pxo + p.slot, RT_PX_BUSY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    x = __hip_atomic_exchange(cs.pxo + p.slot, RT_PX_BUSY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     const uint32_t owed = x & RT_PX_PASSES;
-                    __hip_atomic_fetch_max(st.ret_ctr + 5, owed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_fetch_add(st.ret_ctr + 6, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    atomicAdd(fr.dev_stats + RT_DEV_OWED_PIXELS, 1ull);
-                    atomicAdd(fr.dev_stats + RT_DEV_OWED_PASSES, (unsigned long long)owed);
+                    __hip_atomic_fetch_max(cs.ret_ctr + 5, owed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_add(cs.ret_ctr + 6, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const RtDevFrame cf = WF_COLD_FRAME(fr);
+                    atomicAdd(cf.dev_stats + RT_DEV_OWED_PIXELS, 1ull);
+                    atomicAdd(cf.dev_stats + RT_DEV_OWED_PASSES, (unsigned long long)owed);
                     p.passes_left = (int)owed;
-                    const Vec3D fb = fr.fb[p.slot];
-                    const float sq = fr.sq[p.slot];
-                    const int count = fr.count[p.slot];
-                    if (start_sample<COUNT>(fr, cam, (int)p.slot, p.passes_left, p.rng, fb, sq, count, p.ro, p.rd,
+                    const Vec3D fb = cf.fb[p.slot];
+                    const float sq = cf.sq[p.slot];
+                    const int count = cf.count[p.slot];
+                    if (start_sample<COUNT>(cf, WF_COLD_CAM(cam), (int)p.slot, p.passes_left, p.rng, fb, sq, count, p.ro, p.rd,
                                             c)) {
                         begin_path(p);
                         rel = false;
@@ -162,6 +164,9 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
             const bool idle = !active && !(chained && exhausted);
             const unsigned long long im = __ballot(idle);
             if (im) {
+                WfCold &cs = WF_COLD(st);
+                unsigned long long *const ret_word = reinterpret_cast<unsigned long long *>(cs.ret_ctr);
+                uint32_t *const ret_claimed = cs.ret_ctr + 2;
                 const int leader = __ffsll((long long)im) - 1;
                 uint32_t base = 0, got = 0;
                 if (lane == leader) {
@@ -170,7 +175,8 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
                         (uint32_t)__hip_atomic_load(ret_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     const uint32_t want_n = (uint32_t)__popcll(im);
                     uint32_t take = r > c0 ? (r - c0 < want_n ? r - c0 : want_n) : 0u;
-                    if (take && chained && __hip_atomic_load(fetch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n)
+                    if (take && chained &&
+                        __hip_atomic_load(cs.counts + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n)
                         take = 0u;
                     if (take && __hip_atomic_compare_exchange_strong(ret_claimed, &c0, c0 + take, __ATOMIC_RELAXED,
                                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
@@ -189,29 +195,30 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
                     unsigned long long v = 0;
                     bool pub = false;
                     for (uint32_t spin = 0; spin < WF_SPIN_TRIPS; ++spin) {
-                        v = __hip_atomic_load(st.ret_ring + e % st.long_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        v = __hip_atomic_load(cs.ret_ring + e % cs.long_cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         pub = (uint32_t)(v >> 32) == e + 1u;
                         if (pub) break;
                         __builtin_amdgcn_s_sleep(1);
                     }
                     if (!pub) {
-                        atomicAdd(fr.dev_stats + RT_DEV_LONG_QUIT, 1ull);
+                        atomicAdd(WF_COLD_FRAME(fr).dev_stats + RT_DEV_LONG_QUIT, 1ull);
                     } else {
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        __hip_atomic_fetch_sub(st.ret_ctr + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_fetch_sub(cs.ret_ctr + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         active = true;
-                        first_ray(st, fr, (uint32_t)v, p);
+                        const RtDevFrame cf = WF_COLD_FRAME(fr);
+                        first_ray(cs, cf, (uint32_t)v, p);
                         // back from wf_long: no longer OUT but BUSY (this lane's); plus the passes chained
                         // calls queued meanwhile
-                        const uint32_t owed = __hip_atomic_exchange(st.pxo + (uint32_t)v, RT_PX_BUSY, __ATOMIC_RELAXED,
+                        const uint32_t owed = __hip_atomic_exchange(cs.pxo + (uint32_t)v, RT_PX_BUSY, __ATOMIC_RELAXED,
                                                                     __HIP_MEMORY_SCOPE_AGENT);
                         p.passes_left += (int)(owed & RT_PX_PASSES);
                         if (owed & RT_PX_PASSES) { // (RT_DEBUG_CALL_LOG: most passes owed, pixels owed; RtDeviations)
-                            __hip_atomic_fetch_max(st.ret_ctr + 5, owed & RT_PX_PASSES, __ATOMIC_RELAXED,
+                            __hip_atomic_fetch_max(cs.ret_ctr + 5, owed & RT_PX_PASSES, __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_fetch_add(st.ret_ctr + 6, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            atomicAdd(fr.dev_stats + RT_DEV_OWED_PIXELS, 1ull);
-                            atomicAdd(fr.dev_stats + RT_DEV_OWED_PASSES, (unsigned long long)(owed & RT_PX_PASSES));
+                            __hip_atomic_fetch_add(cs.ret_ctr + 6, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            atomicAdd(cf.dev_stats + RT_DEV_OWED_PIXELS, 1ull);
+                            atomicAdd(cf.dev_stats + RT_DEV_OWED_PASSES, (unsigned long long)(owed & RT_PX_PASSES));
                         }
                     }
                 }
@@ -226,10 +233,12 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
             // pixels)
             bool claim = !active && !rel && !exhausted, started = false, acq = false;
             while (__any(claim)) {
+                WfCold &cs = WF_COLD(st);
+                const RtDevFrame cf = WF_COLD_FRAME(fr);
                 const unsigned long long m = __ballot(claim);
                 const int leader = __ffsll((long long)m) - 1;
                 uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
+                if (lane == leader) base = atomicAdd(cs.counts + 4, (uint32_t)__popcll(m));
                 base = __shfl(base, leader);
                 if (claim) {
                     const uint32_t e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -237,17 +246,17 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
                     if (e >= n) {
                         claim = false;
                         exhausted = true;
-                    } else if (e < n_heavy ? (slot = (int)st.heavy_list[e], true)
-                                           : fresh_pixel(fr, e - n_heavy, slot) &&
-                                                 !(st.heavy_list && st.listed[slot] == st.call_id)) {
-                        uint32_t x = __hip_atomic_load(st.pxo + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    } else if (e < n_heavy ? (slot = (int)cs.heavy_list[e], true)
+                                           : fresh_pixel(cf, e - n_heavy, slot) &&
+                                                 !(cs.heavy_list && cs.listed[slot] == cs.call_id)) {
+                        uint32_t x = __hip_atomic_load(cs.pxo + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         while (true) {
                             if (x & (RT_PX_OUT | RT_PX_BUSY)) { // held: owed this call's passes
-                                if (__hip_atomic_compare_exchange_strong(st.pxo + slot, &x, x + (uint32_t)fr.passes,
+                                if (__hip_atomic_compare_exchange_strong(cs.pxo + slot, &x, x + (uint32_t)cf.passes,
                                                                          __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                                                          __HIP_MEMORY_SCOPE_AGENT))
                                     break;
-                            } else if (__hip_atomic_compare_exchange_strong(st.pxo + slot, &x, RT_PX_BUSY,
+                            } else if (__hip_atomic_compare_exchange_strong(cs.pxo + slot, &x, RT_PX_BUSY,
                                                                             __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                                                             __HIP_MEMORY_SCOPE_AGENT)) {
                                 claim = false;
@@ -268,23 +277,24 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
             // boundary is the release / acquire.)
             if (__any(acq)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             if (started) { // the pixel's state and its first pass (wf_start's)
+                const RtDevFrame cf = WF_COLD_FRAME(fr);
                 const uint32_t slot = p.slot;
-                p.rng = ld_sc1(fr.rng + slot);
+                p.rng = ld_sc1(cf.rng + slot);
                 Vec3D fb = rt_v3(0.0f, 0.0f, 0.0f);
                 float sq = 0.0f;
                 int count = 0;
-                if (fr.reset) { // reset_frame (rt/render.cuh:18-34)
-                    fr.fb[slot] = fb;
-                    fr.sq[slot] = sq;
-                    fr.count[slot] = count;
+                if (cf.reset) { // reset_frame (rt/render.cuh:18-34)
+                    cf.fb[slot] = fb;
+                    cf.sq[slot] = sq;
+                    cf.count[slot] = count;
                 } else {
-                    const uint32_t *f3 = reinterpret_cast<const uint32_t *>(fr.fb + slot);
+                    const uint32_t *f3 = reinterpret_cast<const uint32_t *>(cf.fb + slot);
                     fb = rt_v3(__uint_as_float(ld_sc1(f3)), __uint_as_float(ld_sc1(f3 + 1)), __uint_as_float(ld_sc1(f3 + 2)));
-                    sq = __uint_as_float(ld_sc1(reinterpret_cast<const uint32_t *>(fr.sq + slot)));
-                    count = (int)ld_sc1(reinterpret_cast<const uint32_t *>(fr.count + slot));
+                    sq = __uint_as_float(ld_sc1(reinterpret_cast<const uint32_t *>(cf.sq + slot)));
+                    count = (int)ld_sc1(reinterpret_cast<const uint32_t *>(cf.count + slot));
                 }
-                p.passes_left = fr.passes;
-                if (start_sample<COUNT>(fr, cam, (int)slot, p.passes_left, p.rng, fb, sq, count, p.ro, p.rd, c)) {
+                p.passes_left = cf.passes;
+                if (start_sample<COUNT>(cf, WF_COLD_CAM(cam), (int)slot, p.passes_left, p.rng, fb, sq, count, p.ro, p.rd, c)) {
                     begin_path(p);
                     active = true;
                 } else {
@@ -295,9 +305,10 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
             const bool need = !active && !exhausted;
             const unsigned long long m = __ballot(need);
             if (m) {
+                WfCold &cs = WF_COLD(st);
                 const int leader = __ffsll((long long)m) - 1;
                 uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
+                if (lane == leader) base = atomicAdd(cs.counts + 4, (uint32_t)__popcll(m));
                 base = __shfl(base, leader);
                 if (need) {
                     const uint32_t e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -305,13 +316,16 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
                         exhausted = true;
                     } else {
                         active = true;
-                        first_ray(st, fr, st.q_slot[q][e], p);
+                        first_ray(cs, WF_COLD_FRAME(fr), cs.q_slot[q][e], p);
                     }
                 }
             }
         }
         if (!__any(active || rel)) {
             if (!st.long_return) break; // every lane exhausted
+            WfCold &cs = WF_COLD(st);
+            unsigned long long *const ret_word = reinterpret_cast<unsigned long long *>(cs.ret_ctr);
+            uint32_t *const ret_claimed = cs.ret_ctr + 2;
             if (st.linger == 0ull) { // chained: returns left are the next call's (or the drain's)
                 if (lane == 0) __hip_atomic_fetch_sub(ret_word, 1ull << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
@@ -324,17 +338,17 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
             int leave = 0;
             if (lane == 0) {
                 if (idle_since == 0) idle_since = __builtin_amdgcn_s_memrealtime();
-                if (__hip_atomic_load(st.long_ctr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+                if (__hip_atomic_load(cs.long_ctr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
                     ++quiet_trips;
                 else
                     quiet_trips = 0;
                 ++idle_trips;
                 bool out = quiet_trips < WF_FIN_QUIET_TRIPS && idle_trips < WF_FIN_LINGER_TRIPS &&
-                           __hip_atomic_load(st.ret_ctr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+                           __hip_atomic_load(cs.ret_ctr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
                 // only WF_FIN_LINGER_WAVES waves linger (a seat each, kept until they leave): the
                 // others leave their slots to wf_long, which the deep paths are waiting for
                 if (out && !seated) {
-                    if (__hip_atomic_fetch_add(st.ret_ctr + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
+                    if (__hip_atomic_fetch_add(cs.ret_ctr + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
                         WF_FIN_LINGER_WAVES)
                         seated = true;
                     else
@@ -348,7 +362,7 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
                     leave = 1;
                     // (pixels still out: wf_long, finding no finisher alive, finishes them itself)
-                    if (out) atomicAdd(fr.dev_stats + RT_DEV_LINGER_EXP, 1ull);
+                    if (out) atomicAdd(WF_COLD_FRAME(fr).dev_stats + RT_DEV_LINGER_EXP, 1ull);
                 }
             }
             if (__shfl(leave, 0)) break;
@@ -394,31 +408,36 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
                 h ^= h >> 12;
                 const bool rec = (h & st.chk_mask) == 0u;
                 if (__any(rec)) {
-                    const uint32_t i = wave_append(st.chk_ctr, rec);
-                    if (rec && i < st.chk_cap) {
-                        st.chk[3 * (size_t)i] =
-                            RtF4{p.ro.x, p.ro.y, p.ro.z, __int_as_float(st.chk_fault ? (hit >= 0 ? hit ^ 1 : 0) : hit)};
-                        st.chk[3 * (size_t)i + 1] = RtF4{p.rd.x, p.rd.y, p.rd.z, bx};
-                        st.chk[3 * (size_t)i + 2] = RtF4{by, bz, 0.0f, 0.0f};
+                    WfCold &cs = WF_COLD(st);
+                    const uint32_t i = wave_append(cs.chk_ctr, rec);
+                    if (rec && i < cs.chk_cap) {
+                        cs.chk[3 * (size_t)i] =
+                            RtF4{p.ro.x, p.ro.y, p.ro.z, __int_as_float(cs.chk_fault ? (hit >= 0 ? hit ^ 1 : 0) : hit)};
+                        cs.chk[3 * (size_t)i + 1] = RtF4{p.rd.x, p.rd.y, p.rd.z, bx};
+                        cs.chk[3 * (size_t)i + 2] = RtF4{by, bz, 0.0f, 0.0f};
                     }
                 }
             }
             if (done) {
-                const bool want = shade_step<COUNT>(sc, fr, cam, p, hit, bx, by, bz, limit, c);
+                const RtDevFrame cf = WF_COLD_FRAME(fr);
+                const bool want = shade_step<COUNT>(sc, cf, WF_COLD_CAM(cam), p, hit, bx, by, bz, limit, c);
                 // a path deeper than long_depth goes on in wf_long (64 lanes per ray)
                 to_long = want && st.long_depth > 0 && p.depth > st.long_depth;
-                if (!want || to_long) store_regs(st, fr, p);
+                if (!want || to_long) store_regs(WF_COLD(st), cf, p);
                 if (!want) {
                     active = false;
                     rel = st.fresh != 0; // (the pixel's passes are done: let go at the top of the loop)
                 }
             }
         }
-        if (__any(to_long) && publish_long_capped(st, to_long, p.slot, p.ro, p.rd) && to_long) {
-            active = false;
-            if (st.heavy) { // (first in the next call's list: the more hand-offs, the earlier)
-                const uint8_t h = st.heavy[p.slot];
-                if (h < 255) st.heavy[p.slot] = (uint8_t)(h + 1);
+        if (__any(to_long)) {
+            WfCold &cs = WF_COLD(st);
+            if (publish_long_capped(cs, to_long, p.slot, p.ro, p.rd) && to_long) {
+                active = false;
+                if (cs.heavy) { // (first in the next call's list: the more hand-offs, the earlier)
+                    const uint8_t h = cs.heavy[p.slot];
+                    if (h < 255) cs.heavy[p.slot] = (uint8_t)(h + 1);
+                }
             }
         }
     }
@@ -426,11 +445,12 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
         flush_counters(c, fr.counters);
         flush_cert_counters(c, fr.dev_stats);
     }
-    if (st.span && lane == 0) atomicMax(st.span + 1, __builtin_amdgcn_s_memrealtime());
-    if (st.fin_live) { // this wave's hand-offs are published: the persistent wf_long may stop once all are past here
+    WfCold &ce = WF_COLD(st);
+    if (ce.span && lane == 0) atomicMax(ce.span + 1, __builtin_amdgcn_s_memrealtime());
+    if (ce.fin_live) { // this wave's hand-offs are published: the persistent wf_long may stop once all are past here
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        if (lane == 0) __hip_atomic_fetch_sub(st.fin_live, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0) __hip_atomic_fetch_sub(ce.fin_live, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 

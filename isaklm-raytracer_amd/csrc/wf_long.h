@@ -45,7 +45,8 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
     Cnt c;
     if (COUNT) c.zero();
     const int limit = fr.max_depth > 0 ? fr.max_depth : RT_WATCHDOG_BOUNCES;
-    uint32_t *const reserved = st.long_ctr, *const claimed = st.long_ctr + 1, *const running = st.long_ctr + 3;
+    // (RT_COLD_ARGS, wf_state.h: a bounce reads st.long_wide and st.long_return from registers; the claim, the
+    // return and the release read their fields of the state where they use them, through WF_COLD)
     const bool persist = st.fin_live != nullptr;
     unsigned long long t_idle = __builtin_amdgcn_s_memrealtime(); // (chain window: since entries last flowed)
     unsigned long long t_net = t_idle; // safety net: since anything that could still bring work last held
@@ -60,6 +61,8 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
         RtF4 ro4{0, 0, 0, 0}, rd4{0, 0, 0, 0};
         int quit = 0;
         if (lane == 0) {
+            WfCold &cs = WF_COLD(st);
+            uint32_t *const reserved = cs.long_ctr, *const claimed = cs.long_ctr + 1, *const running = cs.long_ctr + 3;
             while (true) {
                 const unsigned long long now = __builtin_amdgcn_s_memrealtime();
                 ++n_idle;
@@ -67,12 +70,12 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
                 // (producers first: once they are all past their last hand-off,
                 // `reserved` read after this acquire holds every entry.)  A finisher
                 // that has not started is not waited for (WF_LONG_START_TRIPS below)
-                const uint32_t fl = persist ? __hip_atomic_load(st.fin_live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+                const uint32_t fl = persist ? __hip_atomic_load(cs.fin_live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
                 const bool unstarted = persist && !(fl & WF_FIN_STARTED);
                 const bool producing = persist && !unstarted && (fl & ~WF_FIN_STARTED) != 0u;
                 const bool others = __hip_atomic_load(running, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
                 const bool chain_open =
-                    persist && __hip_atomic_load(st.chain_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+                    persist && __hip_atomic_load(cs.chain_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
                 if (persist && !producing && !unstarted) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                 e = __hip_atomic_load(claimed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const uint32_t rw = __hip_atomic_load(reserved, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -92,18 +95,18 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
                 // past its last hand-off and no chain open (or its window over)
                 const bool window_over = (now - t_idle > WF_LONG_CHAIN_IDLE || n_idle > WF_LONG_CHAIN_TRIPS) && !others;
                 const bool done = persist && (closed || (!producing && !unstarted && (!chain_open || window_over)));
-                if (st.debug_quit) { // (tests: as if the net fired at once)
+                if (cs.debug_quit) { // (tests: as if the net fired at once)
                     quit = 2;
                     break;
                 }
                 if (e < r) {
-                    const uint32_t k = e % st.long_cap;
+                    const uint32_t k = e % cs.long_cap;
                     const unsigned long long v =
-                        __hip_atomic_load(st.long_ent + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_load(cs.long_ent + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if ((uint32_t)(v >> 32) == e + 1u) { // published: acquire, read, then claim
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        ro4 = ldf4(st.long_ray + 2 * (size_t)k);
-                        rd4 = ldf4(st.long_ray + 2 * (size_t)k + 1);
+                        ro4 = ldf4(cs.long_ray + 2 * (size_t)k);
+                        rd4 = ldf4(cs.long_ray + 2 * (size_t)k + 1);
                         slot = (uint32_t)v;
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         uint32_t expect = e;
@@ -162,7 +165,7 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
         p.slot = 0;
         p.ro = p.rd = rt_v3(0, 0, 0);
         if (lane == 0) {
-            load_regs(st, fr, slot, p);
+            load_regs(WF_COLD(st), fr, slot, p);
             p.ro = ld3(ro4);
             p.rd = ld3(rd4);
         }
@@ -217,19 +220,20 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
             }
             want = 0;
             if (lane == 0) {
-                want = shade_step<COUNT>(sc, fr, cam, p, hit, bx, by, bz, limit, c) ? 1 : 0;
+                want = shade_step<COUNT>(sc, fr, WF_COLD_CAM(cam), p, hit, bx, by, bz, limit, c) ? 1 : 0;
                 if (!want && st.long_return) {
                     // the pixel's passes are done: run the passes chained calls owe it, or
                     // release it — its state stored and released before the word says so
+                    WfCold &cs = WF_COLD(st);
                     while (true) {
-                        store_regs(st, fr, p);
+                        store_regs(cs, fr, p);
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                         uint32_t x = RT_PX_OUT;
-                        if (__hip_atomic_compare_exchange_strong(st.pxo + p.slot, &x, RT_PX_LONGDONE, __ATOMIC_RELAXED,
+                        if (__hip_atomic_compare_exchange_strong(cs.pxo + p.slot, &x, RT_PX_LONGDONE, __ATOMIC_RELAXED,
                                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
                             break;
-                        x = __hip_atomic_exchange(st.pxo + p.slot, RT_PX_OUT, __ATOMIC_RELAXED,
+                        x = __hip_atomic_exchange(cs.pxo + p.slot, RT_PX_OUT, __ATOMIC_RELAXED,
                                                   __HIP_MEMORY_SCOPE_AGENT);
                         p.passes_left = (int)(x & RT_PX_PASSES);
                         if (x & RT_PX_PASSES) { // (RtDeviations: owed passes, run here in the pixel's order)
@@ -239,7 +243,7 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
                         const Vec3D fb = fr.fb[p.slot];
                         const float sq = fr.sq[p.slot];
                         const int count = fr.count[p.slot];
-                        if (start_sample<COUNT>(fr, cam, (int)p.slot, p.passes_left, p.rng, fb, sq, count, p.ro, p.rd,
+                        if (start_sample<COUNT>(fr, WF_COLD_CAM(cam), (int)p.slot, p.passes_left, p.rng, fb, sq, count, p.ro, p.rd,
                                                 c)) { // as shade_step's next pass
                             p.T = rt_v3(1.0f, 1.0f, 1.0f);
                             p.L = rt_v3(0.0f, 0.0f, 0.0f);
@@ -260,9 +264,10 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
                 // drain finisher lingers (WF_FIN_LINGER) while a pixel is out, so a return
                 // reserved just as its clear of the flag lands is still taken.
                 if (want && st.long_return && p.depth == 1 && !p.shadow) {
-                    unsigned long long *const ret_word = reinterpret_cast<unsigned long long *>(st.ret_ctr);
-                    if (st.linger == 0ull &&
-                        __hip_atomic_load(st.chain_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
+                    WfCold &cs = WF_COLD(st);
+                    unsigned long long *const ret_word = reinterpret_cast<unsigned long long *>(cs.ret_ctr);
+                    if (cs.linger == 0ull &&
+                        __hip_atomic_load(cs.chain_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
                         want = 2;
                         ret_e = (uint32_t)__hip_atomic_fetch_add(ret_word, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
@@ -281,28 +286,29 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_LONG_WAVES) wf_long(RtDevScene sc
             if (want != 1) break;
         }
         if (lane == 0) {
-            if (st.long_log && e < 65535u) {
-                unsigned long long *L = st.long_log + 4 + 4 * (size_t)e;
+            WfCold &cs = WF_COLD(st);
+            if (cs.long_log && e < 65535u) {
+                unsigned long long *L = cs.long_log + 4 + 4 * (size_t)e;
                 L[0] = t_claim;
                 L[1] = __builtin_amdgcn_s_memrealtime();
                 L[2] = bounces;
                 L[3] = p.slot;
             }
             if (want == 2) { // back to the finishers: its state and next ray, then its ring entry
-                store_regs(st, fr, p);
-                st.ro[p.slot] = p.ro;
-                st.cont[p.slot] = p.rd;
+                store_regs(cs, fr, p);
+                cs.ro[p.slot] = p.ro;
+                cs.cont[p.slot] = p.rd;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(st.ret_ring + ret_e % st.long_cap, ((unsigned long long)(ret_e + 1u) << 32) | p.slot,
+                __hip_atomic_store(cs.ret_ring + ret_e % cs.long_cap, ((unsigned long long)(ret_e + 1u) << 32) | p.slot,
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else if (st.long_return) { // done and released above (its state may already be another's)
-                __hip_atomic_fetch_sub(st.ret_ctr + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_sub(cs.ret_ctr + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
-                store_regs(st, fr, p);
+                store_regs(cs, fr, p);
             }
-            __hip_atomic_fetch_sub(running, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_sub(cs.long_ctr + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         t_idle = __builtin_amdgcn_s_memrealtime();
         n_idle = 0;

@@ -67,8 +67,9 @@ struct PathRegsL {
     Vec3D ro, rd;
 };
 
-template <typename P>
-__device__ __forceinline__ void load_regs(const WfState &st, const RtDevFrame &fr, uint32_t slot, P &p)
+// (ST: WfState, or the kernel's own copy of it read in place — wf_state.h wf_cold_state)
+template <typename ST, typename P>
+__device__ __forceinline__ void load_regs(const ST &st, const RtDevFrame &fr, uint32_t slot, P &p)
 {
     p.slot = slot;
     const uint32_t flags = st.flags[slot];
@@ -90,8 +91,8 @@ __device__ __forceinline__ void load_regs(const WfState &st, const RtDevFrame &f
     }
 }
 
-template <typename P>
-__device__ __forceinline__ void store_regs(const WfState &st, const RtDevFrame &fr, const P &p)
+template <typename ST, typename P>
+__device__ __forceinline__ void store_regs(const ST &st, const RtDevFrame &fr, const P &p)
 {
     const uint32_t slot = p.slot;
     fr.rng[slot] = p.rng;
@@ -110,8 +111,8 @@ __device__ __forceinline__ void store_regs(const WfState &st, const RtDevFrame &
 
 // a path of a path list with its first pending ray in p.ro / p.rd (the
 // shadow ray if one is pending: its direction recomputed as it was set up)
-template <typename P>
-__device__ __forceinline__ void first_ray(const WfState &st, const RtDevFrame &fr, uint32_t slot, P &p)
+template <typename ST, typename P>
+__device__ __forceinline__ void first_ray(const ST &st, const RtDevFrame &fr, uint32_t slot, P &p)
 {
     load_regs(st, fr, slot, p);
     p.ro = st.ro[slot];

@@ -291,6 +291,70 @@ struct WfState {
     int long_wide;
 };
 
+// RT_COLD_ARGS: what a loop trip of wf_finish_bvh does not read leaves the registers.  A kernel's by-value
+// arguments are loaded into scalar registers at its entry and stay live to their last use: the finisher's ~190
+// argument dwords against ~100 registers put 200 of them into vector-register lanes (v_writelane / v_readlane
+// around every use, three VGPRs held for them while 12 others went to scratch).  The fields only rare paths
+// read — the hand-off and return rings and their counters, the heavy list, the ownership words, the path
+// state arrays of store_regs / first_ray, the guard's record buffer, span and the debug fields — are now read
+// where they are used, from the kernel's own argument block: the kernarg segment is device memory the
+// dispatch wrote for this launch, read-only to the kernel, and its address is wave-uniform, so each read is
+// one scalar load through the scalar cache.  No second copy of the state exists and the host does nothing
+// new.  wf_cold_state() hands out the WfState argument in place; its address passes through an empty asm
+// so that the compiler cannot move the loads back to the kernel's entry.  For the kernels whose arguments
+// start (RtDevScene, RtDevFrame, RtDevCamera, WfState): wf_finish_bvh and wf_long (the offset is checked
+// against the code object's own argument table in tests/test_fin_resources.py).
+#ifndef RT_COLD_ARGS
+#define RT_COLD_ARGS 1 // 0 (a HIP compile flag, for A/B): every field from the by-value argument
+                       // (NOT the build before the switch: the source around the reads — the cs / cf locals, ret_word
+                       // recomputed where it is used — allocates differently even with the macros the identity:
+                       // 207 SGPR / 23 VGPR spills in wf_finish_bvh<false, 4> against 200 / 12 before.  A bisect
+                       // with the switch overstates the gain; compare with the commit before it, as DESIGN §9 does)
+#endif
+constexpr size_t wf_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr size_t WF_KERNARG_FRAME = wf_align_up(sizeof(RtDevScene), alignof(RtDevFrame));
+constexpr size_t WF_KERNARG_CAMERA = wf_align_up(WF_KERNARG_FRAME + sizeof(RtDevFrame), alignof(RtDevCamera));
+constexpr size_t WF_KERNARG_STATE = wf_align_up(WF_KERNARG_CAMERA + sizeof(RtDevCamera), alignof(WfState));
+// (the values tests/test_fin_resources.py finds in the built kernels' argument tables)
+static_assert(WF_KERNARG_FRAME == 248 && WF_KERNARG_CAMERA == 360 && WF_KERNARG_STATE == 416 && sizeof(WfState) == 344,
+              "kernarg layout of (RtDevScene, RtDevFrame, RtDevCamera, WfState, ...): update tests/test_fin_resources.py");
+#if RT_COLD_ARGS && defined(__HIP_DEVICE_COMPILE__)
+// The empty `asm volatile` with "+s" is all that keeps the loads at their use: it makes the pointer opaque and
+// cannot itself be hoisted or merged.  A compiler that saw through it would load the fields at the entry again
+// and the spills would return — nothing would break, and tests/test_fin_resources.py's bound on sgpr_spill_count
+// (the value this build reaches) is what would fail: that test failing after a compiler upgrade means this.
+typedef const RT_CONST WfState WfCold;
+__device__ __forceinline__ WfCold &wf_cold_state()
+{
+    const RT_CONST char *k = (const RT_CONST char *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return *reinterpret_cast<WfCold *>(k + WF_KERNARG_STATE);
+}
+// (the camera, read once per sample start: a copy in registers for that block only)
+__device__ __forceinline__ RtDevCamera wf_cold_camera()
+{
+    const RT_CONST char *k = (const RT_CONST char *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return *reinterpret_cast<const RT_CONST RtDevCamera *>(k + WF_KERNARG_CAMERA);
+}
+// (the frame, for the blocks that start a sample, claim a pixel or shade: live inside such a block, not across
+// the traversal loops; the compiler loads only the fields the block reads)
+__device__ __forceinline__ RtDevFrame wf_cold_frame()
+{
+    const RT_CONST char *k = (const RT_CONST char *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return *reinterpret_cast<const RT_CONST RtDevFrame *>(k + WF_KERNARG_FRAME);
+}
+#define WF_COLD(st) wf_cold_state()
+#define WF_COLD_CAM(cam) wf_cold_camera()
+#define WF_COLD_FRAME(fr) wf_cold_frame()
+#else
+typedef const WfState WfCold;
+#define WF_COLD(st) (st)
+#define WF_COLD_CAM(cam) (cam)
+#define WF_COLD_FRAME(fr) (fr)
+#endif
+
 namespace {
 
 __device__ __forceinline__ uint32_t lanemask_lt() { return (uint32_t)__lane_id(); }
@@ -330,8 +394,8 @@ __device__ __forceinline__ void enqueue_path(const WfState &st, int q, bool want
 // publish ring entry e of the long-path hand-off: the ray, then (after this
 // wave's stores are drained and released: the XCD's L2 written back,
 // MI355X_MICROARCH.md hand-off rules) the tag wf_long's claims check
-__device__ __forceinline__ void long_publish(const WfState &st, bool to_long, uint32_t e, uint32_t slot, Vec3D o,
-                                             Vec3D d)
+template <typename ST>
+__device__ __forceinline__ void long_publish(const ST &st, bool to_long, uint32_t e, uint32_t slot, Vec3D o, Vec3D d)
 {
     const uint32_t k = e % st.long_cap;
     if (to_long) {
@@ -364,7 +428,8 @@ __device__ __forceinline__ void publish_long(const WfState &st, bool to_long, ui
 // (wave-uniform) when the entries would not fit or the ring is closed: the
 // lanes then keep their paths.  The path state is stored by the caller first; the pixel is OUT
 // (pxo) from here until a finisher takes it back or wf_long finishes it.
-__device__ __forceinline__ bool publish_long_capped(const WfState &st, bool to_long, uint32_t slot, Vec3D o, Vec3D d)
+template <typename ST>
+__device__ __forceinline__ bool publish_long_capped(const ST &st, bool to_long, uint32_t slot, Vec3D o, Vec3D d)
 {
     const unsigned long long m = __ballot(to_long);
     const int lane = __lane_id();
