@@ -252,3 +252,136 @@ def adversarial_scene(d, variant="far", seed=1):
         f.write(f"mesh adv.obj adv.mat {ox!r} {oy!r} {oz!r} 0.1 0 {sc!r} 0\n"
                 f"camera {cam[0]!r} {cam[1]!r} {cam[2]!r} 0.1 0 0.8 0.0001\n")
     return p
+
+
+# ------------------------------------------------------------ the material space
+# One box per material: the BSDF's extremes, which no rendered scene reaches otherwise.  Every number is written
+# as a literal that strtof parses to a normal f32 (the reference's std::stof throws on a denormal result); the
+# denormals arise in the arithmetic: roughness and k of 1e-20 square to 1e-40, an albedo of 1e-21 gives a squared
+# luminance of about 1e-41.
+def _mat(albedo="0.8 0.8 0.8", roughness="0.1", n="1.5", k=None, transparent=False, emittance=None, texture=None):
+    t = f"albedo {albedo}\n"
+    if emittance:
+        t += f"emittance {emittance}\n"
+    t += f"roughness {roughness}\nn {n}\n"
+    if k:
+        t += f"k {k}\n"
+    if transparent:
+        t += "transparent\n"
+    if texture:
+        t += f"texture {texture}\n"
+    return t
+
+
+MATERIALS_TEXTURE = ("textures/box.png", "png_pal8_trns")  # (path in the .mat file, texture_fixtures variant)
+ROOM_MATERIALS = {"wall": _mat("0.75 0.75 0.75", "0.5"), "floor": _mat("0.97 0.97 0.97", "0.5"),
+                  "lamp": _mat("0 0 0", "0.5", emittance="4.0 4.0 4.0")}  # the lamp ends every path that meets it
+
+
+def material_set():
+    """name -> .mat text of the `materials` scene's boxes"""
+    m = {}
+    for r in ("0", "1e-20", "1e-4", "0.05", "0.5", "1", "1.5"):
+        m[f"rough_{r}_dielectric"] = _mat("0.7 0.6 0.5", r)
+        m[f"rough_{r}_glass"] = _mat("0.97 0.97 0.97", r, transparent=True)
+        m[f"rough_{r}_conductor"] = _mat("0.9 0.7 0.3", r, n="1.2", k="3.0")
+    for n in ("1.0", "1.0001", "4", "0.5", "100"):  # 0.5 in the middle of the grid: it transmits within 30 degrees
+        m[f"n_{n}_opaque"] = _mat("0.6 0.7 0.8", n=n)
+        m[f"n_{n}_transparent"] = _mat("0.97 0.97 0.97", n=n, transparent=True)
+    for k in ("1e-20", "1e-3", "0.25", "50"):
+        m[f"k_{k}"] = _mat("0.9 0.8 0.7", n="1.2", k=k)
+    m["albedo_0_opaque"] = _mat("0 0 0")
+    m["albedo_0_transparent"] = _mat("0 0 0", transparent=True)
+    m["albedo_2"] = _mat("2.0 2.0 2.0", "0.5")
+    m["albedo_1e-30"] = _mat("1e-30 1e-30 1e-30", "0.5")
+    m["albedo_1e-21"] = _mat("1e-21 1e-21 1e-21", "0.5")  # squared luminance about 1e-41
+    m["emissive_glass"] = _mat("0.97 0.97 0.97", "0.05", transparent=True, emittance="2.0 1.5 1.0")
+    m["emissive_metal"] = _mat("0.9 0.7 0.3", "0.2", n="1.2", k="3.0", emittance="1.0 1.5 2.0")
+    m["dim_emitter"] = _mat("0.5 0.5 0.5", "0.5", emittance="1e-9 1e-9 1e-9")  # NEE from it onto albedo 1e-30
+    m["guide_n_4"] = _mat("0.999 0.999 0.999", "0.001", n="4", transparent=True)  # smooth and clear: deep paths
+    m["guide_n_100"] = _mat("0.999 0.999 0.999", "0.001", n="100", transparent=True)
+    m["textured"] = _mat("0.9 0.85 0.8", "0.4", texture=MATERIALS_TEXTURE[0])
+    return m
+
+
+def nonfinite_material_set():
+    """the boxes of `materials_nonfinite`: three ordinary materials and the values that make NaN and Inf.  3e38
+    and 1e30 are finite f32 numbers: the overflow happens in the products (3e38 * 3e38, 1e30 * 1e30)"""
+    m = {"plain": _mat("0.7 0.6 0.5", "0.5"), "glass": _mat("0.97 0.97 0.97", "0.01", transparent=True),
+         "gold": _mat("0.9 0.7 0.3", "0.15", n="1.2", k="3.0"),
+         "emittance_3e38": _mat("0.5 0.5 0.5", "0.5", emittance="3e38 3e38 3e38"),
+         "albedo_3e38_diffuse": _mat("3e38 3e38 3e38", "0.5"),
+         "albedo_3e38_glass": _mat("3e38 3e38 3e38", "0.05", transparent=True),
+         "albedo_3e38_metal": _mat("3e38 3e38 3e38", "0.15", n="1.2", k="3.0"),
+         "rough_1e30": _mat("0.7 0.6 0.5", "1e30"),
+         "n_1e30": _mat("0.7 0.6 0.5", n="1e30"),
+         "n_0_opaque": _mat("0.7 0.6 0.5", n="0"),
+         "n_0_transparent": _mat("0.97 0.97 0.97", n="0", transparent=True),
+         "k_1e30": _mat("0.9 0.7 0.3", n="1.2", k="1e30")}
+    return m
+
+
+MATERIALS_GRID = (8, 6)  # boxes across x and z: the frame's 4:3
+# Just under the lamp ceiling, looking straight down at the whole grid, so that what a box top reflects meets
+# the lamp.  Off the symmetry planes, where the KD splits lie: a ray origin on a split plane is a hazard of its
+# own (H5).
+MATERIALS_CAMERA = "0.013 2.4 0.007 0 1.5707964 2.161 0"
+
+
+def materials_scene(d, mats=None, name="materials"):
+    """A room with a floor, four walls and, above a gap, a lamp ceiling; on the floor a grid of small boxes, one
+    material per box in the order of `mats` (default material_set(); the cells beyond the set repeat its first
+    three).  A box is a top and four sides, and the floor closes it, so a transparent one is entered and left.
+    The room is open at the gap between the walls and the lamp: a path whose throughput has become NaN survives
+    every roulette and ends only when it leaves the scene.  The camera looks straight down from under the lamp,
+    so every box top is met close to its normal.  Returns the scene file."""
+    import texture_fixtures
+
+    mats = mats or material_set()
+    os.makedirs(os.path.join(d, "textures"), exist_ok=True)
+    if any(MATERIALS_TEXTURE[0] in t for t in mats.values()):
+        with open(os.path.join(d, MATERIALS_TEXTURE[0]), "wb") as f:
+            f.write(texture_fixtures.variants()[MATERIALS_TEXTURE[1]])
+    with open(os.path.join(d, f"{name}.mat"), "w") as f:
+        f.write("\n".join(f"material {k}\n{t}" for k, t in {**ROOM_MATERIALS, **mats}.items()))
+    nx, nz = MATERIALS_GRID
+    X, Z, Y = nx / 2 + 0.5, nz / 2 + 0.5, 1.5
+    vs, faces = [], []
+
+    def quad(mat, a, b, c, e, uv=False):
+        base = len(vs) + 1
+        vs.extend([a, b, c, e])
+        faces.append(f"usemtl {mat}")
+        faces.append("f " + " ".join(f"{base + j}/{j + 1}" if uv else f"{base + j}" for j in range(4)))
+
+    quad("floor", (-X, 0, -Z), (X, 0, -Z), (X, 0, Z), (-X, 0, Z))
+    quad("wall", (-X, 0, Z), (X, 0, Z), (X, Y, Z), (-X, Y, Z))
+    quad("wall", (-X, 0, -Z), (-X, Y, -Z), (X, Y, -Z), (X, 0, -Z))
+    quad("wall", (X, 0, -Z), (X, Y, -Z), (X, Y, Z), (X, 0, Z))
+    quad("wall", (-X, 0, -Z), (-X, 0, Z), (-X, Y, Z), (-X, Y, -Z))
+    for k in range(36):  # the lamp: a ceiling of strips above the walls (in strips, because the light pick is
+        x0 = -X + 0.25 * k  # uniform over emissive triangles, boxes included)
+        quad("lamp", (x0, 2.5, -Z), (x0 + 0.25, 2.5, -Z), (x0 + 0.25, 2.5, Z), (x0, 2.5, Z))
+    names = list(mats)
+    for cell in range(nx * nz):
+        mat = names[cell] if cell < len(names) else names[cell % 3]
+        cx, cz = cell % nx - nx / 2 + 0.5, cell // nx - nz / 2 + 0.5
+        x0, x1, z0, z1, h = cx - 0.4, cx + 0.4, cz - 0.4, cz + 0.4, 0.4
+        uv = "texture" in mats[mat]
+        quad(mat, (x0, h, z0), (x0, h, z1), (x1, h, z1), (x1, h, z0), uv)
+        quad(mat, (x0, 0, z0), (x0, h, z0), (x1, h, z0), (x1, 0, z0), uv)
+        quad(mat, (x0, 0, z1), (x1, 0, z1), (x1, h, z1), (x0, h, z1), uv)
+        quad(mat, (x0, 0, z0), (x0, 0, z1), (x0, h, z1), (x0, h, z0), uv)
+        quad(mat, (x1, 0, z0), (x1, h, z0), (x1, h, z1), (x1, 0, z1), uv)
+    vt = [(-0.3, -0.2), (1.7, -0.2), (1.7, 1.4), (-0.3, 1.4)]  # past [0, 1]: the mod wrap
+    with open(os.path.join(d, f"{name}.obj"), "w") as f:
+        f.write("\n".join([f"v {x} {y} {z}" for x, y, z in vs] + [f"vt {a} {b}" for a, b in vt] + faces) + "\n")
+    p = os.path.join(d, "scene.txt")
+    lo, hi = np.min(vs, axis=0), np.max(vs, axis=0)
+    with open(p, "w") as f:  # the loader re-centres a mesh on its offset: the mesh's own centre keeps it in place
+        f.write(f"mesh {name}.obj {name}.mat 0 {(lo[1] + hi[1]) / 2} 0 0 0 1 0\ncamera {MATERIALS_CAMERA}\n")
+    return p
+
+
+def materials_nonfinite_scene(d):
+    return materials_scene(d, nonfinite_material_set(), "materials_nonfinite")

@@ -100,6 +100,27 @@ def assert_bitwise(gpu, ref, pixels=None, what=""):
                                f"gpu {a[bad[:3]]} oracle {b[bad[:3]]}")
 
 
+def same_class(a, b):
+    """per element: integers equal; floats bit-equal where the reference b is not NaN, and NaN (of any payload
+    and sign) exactly where it is"""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    if a.dtype != np.float32:
+        return a == b
+    return np.where(np.isnan(b), np.isnan(a), a.view(np.uint32) == b.view(np.uint32))
+
+
+def assert_same_class(gpu, ref, what="", names=("frame_buffer", "squared_luminance", "sample_count", "random_numbers")):
+    """assert_bitwise for frames that hold NaN: a NaN's payload and sign are outside the parity claim (the
+    reference's own differ between its compilers), everything else is not — a NaN where the reference is finite
+    or infinite, or the reverse, fails like any other bit"""
+    for name, a, b in zip(names, gpu, ref):
+        ok = same_class(a, b)
+        bad = np.nonzero(~ok.reshape(len(ok), -1).all(axis=1))[0]
+        assert len(bad) == 0, (f"{what} {name}: {len(bad)} of {len(ok)} elements differ; first {bad[:8]}: "
+                               f"gpu {np.asarray(a)[bad[:3]]} reference {np.asarray(b)[bad[:3]]}")
+
+
 def rel_linf(gpu_fb, gpu_cnt, ref_fb, ref_cnt):
     """L-infinity of per-channel relative radiance error (fb/count), north_star's 1e-4 bar."""
     a = gpu_fb / np.maximum(gpu_cnt, 1)[:, None]

@@ -61,11 +61,20 @@ FRAME_CASES = {
     "trap": (helpers.make_trap_scene, {"passes": [4]}),  # deep paths (wf_long, the deep bounded traversal)
     "features": (lambda d: os.path.join(HERE, "golden", "features", "scene.txt"), {"passes": [4]}),
     "cornell_blob": (lambda d: helpers.scene_path("cornell_blob"), {"passes": [4]}),  # wide BVH, T* certificate
+    "materials": (hazards.materials_scene, {"passes": [4, 4]}),  # the BSDF's extremes, one box each; finite frames
 }
+# Frames with NaN and Inf in them (emittance and albedo of 3e38; roughness, n and k of 1e30; n of 0).  Kept out of
+# FRAME_CASES: what loops over that compares bit-strictly, and a NaN's payload and sign are outside the parity
+# claim (same_bits here, helpers.assert_same_class on the GPU side: a NaN equals any NaN, all else bit for bit).
+NONFINITE_CASES = {
+    "materials_nonfinite": (hazards.materials_nonfinite_scene, {"passes": [3, 3], "adaptive": True, "min_samples": 2}),
+}
+RENDER_CASES = {**FRAME_CASES, **NONFINITE_CASES}
 RAY_CASE = "rays_cornell"
 RAY_KINDS = (("split", 512), ("axis", 512), ("special", 64), ("inbox", 512))  # test_gpu_query.make_rays' classes
 TRAP_MIN_DEPTH = 256  # the trap's deepest path must be at least this (419 when the fixtures were made)
-ALL_CASES = list(FRAME_CASES) + [RAY_CASE]
+MATERIALS_MIN_DEPTH = 48  # the materials case's deepest path must be at least this (80 when recorded): wf_long
+ALL_CASES = list(RENDER_CASES) + [RAY_CASE]
 
 
 def fixture_path(name):
@@ -120,7 +129,7 @@ class Case:
     def __init__(self, name, d, scene_loader):
         import oracle
 
-        build, o = FRAME_CASES[name] if name != RAY_CASE else (_cornell, {})
+        build, o = RENDER_CASES[name] if name != RAY_CASE else (_cornell, {})
         self.name, self.path = name, build(d)
         register_textures(self.path)
         self.scene = scene_loader(self.path)
@@ -168,7 +177,8 @@ def run_frames(case, scene=None, counters=None):
                          adaptive=case.adaptive, min_samples=case.min_samples, tolerance=case.tolerance)
         if counters is not None and k:
             counters["maxdepth"] = max(counters.get("maxdepth", 0), k["maxdepth"])
-            counters["deep_push"] = counters.get("deep_push", 0) + k["deep_push"]
+            for key in ("deep_push", "watchdog", "cut"):
+                counters[key] = counters.get(key, 0) + k[key]
             for key, v in k["hazards"].items():
                 counters[key] = counters.get(key, 0) + v
         out.append((fb.reshape(n, 3).copy(), sq.copy(), cnt.copy(), rng.copy()))
@@ -223,6 +233,14 @@ class ProductScene:
 TONEMAP_CASE = "cornell"  # its fixture also holds the reference's display bytes of its final frame
 
 
+def zeroed_counts(counts):
+    """a non-finite case's final sample counts with every 7th set to 0 (the display divides by the count):
+    its fixture holds the reference's display bytes of its final frame with these counts"""
+    c = np.array(counts, np.int32)
+    c[::7] = 0
+    return c
+
+
 def record(name, d):
     """(case, what a fixture holds for it), computed by the live reference (oracle/_ref/libref_rt.so)"""
     import reference
@@ -242,6 +260,8 @@ def record(name, d):
                 out[f"call{c}_{key}"] = a
         if name == TONEMAP_CASE:
             out["tonemap_rgba"] = reference.tonemap(frames[-1][0], frames[-1][2])
+        if name in NONFINITE_CASES:
+            out["tonemap_rgba"] = reference.tonemap(frames[-1][0], zeroed_counts(frames[-1][2]))
     out["meta"] = np.array(json.dumps(meta, sort_keys=True))
     return case, out
 
@@ -263,3 +283,46 @@ def same_bits(a, b):
     if a.dtype == np.float32:
         return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
     return bool(np.array_equal(a, b))
+
+
+# ------------------------------------------------------------------ what a case's pixels meet first
+def centre_rays(camera, W, H):
+    """the camera's rays through the pixel centres (path_tracing()'s ray with both jitters 0.5, aperture 0), as
+    (W * H, 6) float32 rows position, direction"""
+    cam = np.asarray(camera, np.float32)
+    cy, sy = np.float32(np.cos(np.float64(cam[3]))), np.float32(np.sin(np.float64(cam[3])))
+    cp, sp = np.float32(np.cos(np.float64(cam[4]))), np.float32(np.sin(np.float64(cam[4])))
+    R = (np.array([[cy, 0, -sy], [0, 1, 0], [sy, 0, cy]], np.float32).T  # rotation_matrix(yaw, pitch), roll 0:
+         @ np.array([[1, 0, 0], [0, cp, sp], [0, -sp, cp]], np.float32).T)  # the reference lists columns
+    t = np.float32(np.tan(np.float64(cam[5]) / 2))
+    y, x = np.mgrid[0:H, 0:W].astype(np.float32)
+    d = np.stack([t * (x + 0.5 - W // 2) / (W // 2), t * (y + 0.5 - H // 2) / (W // 2), np.ones_like(x)], -1)
+    d = (d / np.linalg.norm(d, axis=-1, keepdims=True)).reshape(-1, 3).astype(np.float32) @ R.T
+    return np.concatenate([np.repeat(cam[None, :3], W * H, 0), d], axis=1).astype(np.float32)
+
+
+def first_hits(case):
+    """(rays, trace_rays' rows, material name or None) of the case's centre rays on the oracle; the name is read
+    from the hit triangle's material, matched against the materials of the scene's .mat file"""
+    import oracle
+
+    osc = case.scene if isinstance(case.scene, oracle.OracleScene) else oracle.OracleScene(case.path)
+    rays = centre_rays(case.camera, case.W, case.H)
+    hits = osc.trace_rays(rays)
+    tris = np.frombuffer(osc.arrays()[0], np.uint8).reshape(-1, 152)
+    mat_file = [p for r, p in scene_input_files(case.path) if r.endswith(".mat")][0]
+    names = [ln.split()[1] for ln in open(mat_file).read().splitlines() if ln.startswith("material ")]
+    by_bytes = {}
+    for nm in names:  # albedo, emittance, roughness, n, k, transparent: Triangle bytes 96..133
+        rc_, m = oracle.load_material(mat_file, nm)
+        assert rc_ == 1
+        by_bytes[m.tobytes()] = nm
+    out = []
+    for h in hits:
+        if h[0] != 1:
+            out.append(None)
+            continue
+        t = tris[int(h[1])]
+        key = np.concatenate([t[96:132].copy().view(np.float32), [np.float32(t[132])]]).astype(np.float32).tobytes()
+        out.append(by_bytes[key])
+    return rays, hits, out

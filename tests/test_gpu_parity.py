@@ -16,6 +16,13 @@ import rt
 
 pytestmark = pytest.mark.gpu
 KERNELS = [pytest.param(rt.KERNEL_MEGA, id="mega"), pytest.param(rt.KERNEL_WAVEFRONT, id="wavefront")]
+# (wf_tail, wf_finish_waves, wf_wide) of test_wavefront_finisher_modes and (wf_long_depth, wf_pipelines) of
+# test_wavefront_long_paths_and_pipelines, with their ids; tests/test_gpu_materials.py runs the same sets
+FINISHER_MODES = [(1 << 30, 3, 0), (1 << 30, 3, 3), (1 << 30, 1 << 20, 0), (1 << 30, 1 << 20, -1), (700, 5, 0), (1, 0, 0)]
+FINISHER_MODE_IDS = ["finisher-only-refetch", "finisher-only-refetch-wide-3", "finisher-only-wide",
+                     "finisher-only-1-per-wave-narrow", "late-handoff-refetch", "queues-only"]
+LONG_MODES = [(1, 3), (3, 1), (-1, 2)]
+LONG_MODE_IDS = ["long-handoff-all", "long-handoff-deep-1-pipe", "no-handoff-2-pipes"]
 
 
 @pytest.fixture(scope="module")
@@ -75,10 +82,7 @@ def test_other_trace_variants(variant):
 
 
 @pytest.mark.parametrize("scene", ["room_small", "cornell_blob"])
-@pytest.mark.parametrize("tail,waves,wide", [(1 << 30, 3, 0), (1 << 30, 3, 3), (1 << 30, 1 << 20, 0),
-                                             (1 << 30, 1 << 20, -1), (700, 5, 0), (1, 0, 0)],
-                         ids=["finisher-only-refetch", "finisher-only-refetch-wide-3", "finisher-only-wide",
-                              "finisher-only-1-per-wave-narrow", "late-handoff-refetch", "queues-only"])
+@pytest.mark.parametrize("tail,waves,wide", FINISHER_MODES, ids=FINISHER_MODE_IDS)
 def test_wavefront_finisher_modes(scene, tail, waves, wide):
     """The cooperative finisher (wf_finish_coop) at every hand-off point and
     width: whole call in the finisher with few waves (lanes refetch paths;
@@ -129,8 +133,7 @@ def test_bounded_queue_path_counted():
 
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("scene", ["room_small", "cornell_blob"])
-@pytest.mark.parametrize("long_depth,pipes", [(1, 3), (3, 1), (-1, 2)],
-                         ids=["long-handoff-all", "long-handoff-deep-1-pipe", "no-handoff-2-pipes"])
+@pytest.mark.parametrize("long_depth,pipes", LONG_MODES, ids=LONG_MODE_IDS)
 def test_wavefront_long_paths_and_pipelines(scene, long_depth, pipes):
     """Paths handed to wf_long (every path deeper than 1 or 3 bounces, so the
     cross-kernel hand-off is exercised thousands of times) and the pipeline

@@ -182,7 +182,7 @@ def test_oracle_correct_color_equals_reference(live):
     assert (want == 1.0).any() and ((want > 0) & (want < 12.92 * 0.0031308)).any() and (want > 0.5).any()
 
 
-@pytest.mark.parametrize("name", list(rc.FRAME_CASES))
+@pytest.mark.parametrize("name", list(rc.RENDER_CASES))
 def test_oracle_frames_equal_reference(live, workdir, name):
     """path_tracing() over the case's calls: frame_buffer, squared_luminance, sample_count, random_numbers"""
     case, out = live_record(workdir, name)
@@ -194,10 +194,13 @@ def test_oracle_frames_equal_reference(live, workdir, name):
     assert_same_frames(frames, want, f"{name}: oracle vs reference,")
     if name == rc.TONEMAP_CASE:
         np.testing.assert_array_equal(oracle.tonemap(frames[-1][0], frames[-1][2]), out["tonemap_rgba"])
+    if name in rc.NONFINITE_CASES:
+        np.testing.assert_array_equal(oracle.tonemap(frames[-1][0], rc.zeroed_counts(frames[-1][2])),
+                                      out["tonemap_rgba"])
 
 
 # ------------------------------------------ b. the product's host side vs live
-@pytest.mark.parametrize("name", list(rc.FRAME_CASES))
+@pytest.mark.parametrize("name", list(rc.RENDER_CASES))
 def test_product_host_scene_equals_reference(live, workdir, name):
     """rt.HostScene's triangles (materials, texels) and rt.build_kd_tree's nodes, indices and bounds, byte for
     byte.  (The product makes its light list when it uploads a scene: tests/test_gpu_reference.py compares
@@ -245,6 +248,11 @@ def test_fixture_equals_oracle(workdir, name):
     assert_same_frames(frames, rc.fixture_frames(fx), f"{name}: oracle vs fixture,")
     if name == rc.TONEMAP_CASE:
         np.testing.assert_array_equal(oracle.tonemap(frames[-1][0], frames[-1][2]), fx["tonemap_rgba"])
+    if name in rc.NONFINITE_CASES:
+        np.testing.assert_array_equal(oracle.tonemap(frames[-1][0], rc.zeroed_counts(frames[-1][2])),
+                                      fx["tonemap_rgba"])
+    if name == "materials":  # deep enough for wf_long at the depth tests/test_gpu_materials.py hands paths over
+        assert counters["maxdepth"] >= rc.MATERIALS_MIN_DEPTH, counters
     if name == "trap":  # wf_long and the deep bounded traversal are really on the path
         assert counters["maxdepth"] >= rc.TRAP_MIN_DEPTH, counters
     if name == "h4":
@@ -253,6 +261,75 @@ def test_fixture_equals_oracle(workdir, name):
               "degenerate": "degenerate"}.get(name)
     if hazard:
         assert counters[hazard] > 100, counters
+
+
+# ------------------------- e. the material cases meet their subject (oracle and fixtures only)
+def _pixel_classes(fx):
+    """of the recorded final frame: (pixels with a NaN, with an Inf and no NaN, finite and not black), a pixel
+    being its three frame_buffer floats and its squared_luminance"""
+    fb, sq, _, _ = rc.fixture_frames(fx)[-1]
+    v = np.concatenate([fb, sq[:, None]], axis=1)
+    nan = np.isnan(v).any(axis=1)
+    inf = np.isinf(v).any(axis=1) & ~nan
+    return nan, inf, np.isfinite(v).all(axis=1) & (fb != 0).any(axis=1)
+
+
+def test_materials_case_covers_the_material_space(workdir):
+    """every material of the materials case is what at least 8 pixels' centre rays meet first; every transparent
+    one transmits there (the oracle's scatter on those hits, on the frame's seeds); the frames are finite, and hold f32 denormals (squared luminances of the albedo
+    1e-21 box), which a device that flushed them would not reproduce; no path met the watchdog"""
+    import hazards
+    import independent as ind
+
+    fx = rc.load_fixture("materials")
+    case, _, counters = oracle_case(workdir, "materials")
+    assert counters["maxdepth"] >= rc.MATERIALS_MIN_DEPTH and counters["maxdepth"] < 10_000, counters
+    assert counters["watchdog"] == 0 and counters["cut"] == 0, counters
+    mats = hazards.material_set()
+    for want in ("rough_0_", "rough_1e-20_", "rough_1.5_", "n_1.0_", "n_0.5_", "n_100_", "k_1e-20", "k_50",
+                 "albedo_0_", "albedo_2", "albedo_1e-30", "emissive_glass", "emissive_metal", "textured"):
+        assert any(k.startswith(want) for k in mats), want
+    rays, hits, names = rc.first_hits(case)
+    names = np.array([n or "" for n in names])
+    tris = np.frombuffer(case.scene.arrays()[0], np.uint8).reshape(-1, 152)
+    frames = rc.fixture_frames(fx)
+    for name, text in mats.items():
+        px = np.nonzero(names == name)[0]
+        assert len(px) >= 8, (name, len(px))
+        if "transparent" not in text.split():
+            continue
+        t = tris[hits[px, 1].astype(np.int64)]
+        mat = t[:, 96:132].copy().view(f32).reshape(-1, 9)
+        nrm, tan = hits[px, 5:8], hits[px, 8:11]  # (the bitangent's sign does not matter to the event's type)
+        smp = ti.scatter_samples(mat[:, 0:3], mat[:, 6], mat[:, 7], mat[:, 8], t[:, 132] != 0, hits[px, 2:5], nrm, tan,
+                                 ind.normalize(ind.cross(nrm, tan)))
+        types = ti.oracle_scatter(rays[px, 3:6], smp, np.zeros(len(px), bool), fx["seeds"][px])[2]
+        assert (types == ind.TRANSMISSION).any(), (name, np.bincount(types))
+    for c, arrays in enumerate(frames):
+        for key, a in zip(rc.G_NAMES, arrays):
+            assert a.dtype != f32 or np.isfinite(a).all(), (c, key)
+    sq = frames[-1][1]
+    denormal = (sq != 0) & (np.abs(sq) < np.finfo(f32).tiny)
+    assert (denormal & (names == "albedo_1e-21")).sum() >= 8, (denormal.sum(), set(names[denormal]))
+
+
+def test_nonfinite_case_is_nonfinite(workdir):
+    """the recorded final frame of materials_nonfinite has NaN pixels, Inf pixels, and a good share of ordinary
+    ones; the adaptive test stopped pixels at different counts; every path ended by itself"""
+    import hazards
+
+    for name in rc.NONFINITE_CASES:
+        fx = rc.load_fixture(name)
+        case, _, counters = oracle_case(workdir, name)
+        assert counters["maxdepth"] < 1000 and counters["watchdog"] == 0 and counters["cut"] == 0, counters
+        nan, inf, plain = _pixel_classes(fx)
+        assert nan.sum() >= 50 and inf.sum() >= 50 and plain.sum() * 4 >= len(plain), (nan.sum(), inf.sum(), plain.sum())
+        assert len(np.unique(rc.fixture_frames(fx)[-1][2])) >= 3
+        names = [n for n in rc.first_hits(case)[2] if n]
+        for mat in hazards.nonfinite_material_set():
+            assert names.count(mat) >= 8, (mat, names.count(mat))
+        rgba, zeroed = fx["tonemap_rgba"], rc.zeroed_counts(rc.fixture_frames(fx)[-1][2]) == 0
+        assert zeroed.sum() > 200 and len(np.unique(rgba[:, :3])) > 50
 
 
 def test_fixture_sizes():
