@@ -10,7 +10,8 @@
 // backwards: the result must not depend on the order.
 //
 // Not product code: shared by tests/native/wide_smin_check.cpp (the result
-// against the sequential query's) and tools/deep_ray_work.cpp (the work model).
+// against the sequential query's, host/trace_host.h bvh4_smin) and
+// tools/deep_ray_work.cpp (the work model).  tk_out is bvh4_smin's tk.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -19,10 +20,7 @@
 #include <vector>
 
 #include "../wide_bvh_caps.h"
-#include "bvh_build.h"
-#include "rt_host.h"
-
-#define WSM_TK_TIE (-2)
+#include "trace_host.h"
 
 struct WsmWork {
     int rounds = 0;            // dependent rounds
@@ -38,16 +36,8 @@ inline bool wide_smin_host(const std::vector<RtF4> &wide, int arity, const rt_ho
                            float best0, size_t fcap, size_t lcap, bool reversed, float &best_out, int &tk_out,
                            WsmWork &w)
 {
-    auto bits = [](float f) {
-        uint32_t u;
-        memcpy(&u, &f, 4);
-        return u;
-    };
-    auto fromb = [](uint32_t u) {
-        float f;
-        memcpy(&f, &u, 4);
-        return f;
-    };
+    using trace_host::bitsf;
+    using trace_host::fbits;
     const RtSlab sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, h.bvh_scale));
     struct Item { uint32_t node; float tn; };
     std::vector<Item> F{{0u, -INFINITY}}, Fn;
@@ -67,7 +57,7 @@ inline bool wide_smin_host(const std::vector<RtF4> &wide, int arity, const rt_ho
             for (int k = 0; k < arity; ++k) {
                 const int c = reversed ? arity - 1 - k : k;
                 const RtF4 *rec = &wide[2 * ((size_t)it.node * (size_t)arity + (size_t)c)];
-                const uint32_t ref = bits(rec[1].z);
+                const uint32_t ref = fbits(rec[1].z);
                 float tn;
                 if (!rt_bvh_box(rec[0].x, rec[0].y, rec[0].z, rec[0].w, rec[1].x, rec[1].y, sl, best, tn) ||
                     ref == RT_BVH_EMPTY)
@@ -91,21 +81,21 @@ inline bool wide_smin_host(const std::vector<RtF4> &wide, int arity, const rt_ho
                 if (!rt_tri_plane(h.bvh_a[slot], o, d, INFINITY, s)) continue;
                 if (!(s < best || (s == best && have))) continue;
                 const RtIsectBary &R = h.bvh_bary[slot];
-                if (!rt_tri_bary(R.b, R.c, R.d, fromb(R.rd), o, d, s, cx, cy, cz)) continue;
+                if (!rt_tri_bary(R.b, R.c, R.d, bitsf(R.rd), o, d, s, cx, cy, cz)) continue;
                 if (s == best) w.cross_round = true;
-                const uint32_t sb = bits(s);
+                const uint32_t sb = fbits(s);
                 const unsigned long long mine = (unsigned long long)sb << 32 | slot, old = key;
                 key = mine < key ? mine : key;
                 if ((uint32_t)(old >> 32) == sb) tie = sb < tie ? sb : tie;
             }
         }
         have = key != ~0ull;
-        if (have) best = fromb((uint32_t)(key >> 32));
+        if (have) best = bitsf((uint32_t)(key >> 32));
         F.swap(Fn);
         L.swap(Ln);
         w.leaves = (int)L.size() > w.leaves ? (int)L.size() : w.leaves;
     }
     best_out = best;
-    tk_out = !have ? -1 : (tie == (uint32_t)(key >> 32) ? WSM_TK_TIE : (int)(uint32_t)key);
+    tk_out = !have ? -1 : (tie == (uint32_t)(key >> 32) ? trace_host::TK_TIE : (int)(uint32_t)key);
     return true;
 }

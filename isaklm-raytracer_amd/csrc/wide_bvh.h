@@ -39,7 +39,8 @@
 //
 // kd_bounded_wave, below, is step 3 (the bounded KD traversal) run by the same
 // wave.  tests/native/wide_smin_check.cpp checks a host restatement of the
-// query against the sequential one; tools/deep_ray_work.cpp is its work model.
+// query (host/wide_smin_host.h) against the sequential one (host/trace_host.h
+// bvh4_smin); tools/deep_ray_work.cpp is its work model.
 #pragma once
 #include "bvh_trace.h"
 #include "wide_bvh_caps.h"

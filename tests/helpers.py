@@ -19,6 +19,24 @@ def scene_path(name):
     return p
 
 
+def build_native(outdir, name, link_lib=True, openmp=True):
+    """compiles tests/native/<name>.cpp with the checkers' flags (link_lib: against the built library, which must
+    exist and match the header; openmp: only with link_lib); returns the binary's path"""
+    import subprocess
+
+    out = os.path.join(str(outdir), name)
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(ROOT, "isaklm-raytracer_amd", "csrc"),
+           os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", out]
+    if link_lib:
+        rt.lib()
+        libdir = os.path.dirname(rt.LIB_PATH)
+        cmd += (["-fopenmp"] if openmp else []) + ["-L" + libdir, "-lisaklm_rt", "-Wl,-rpath," + libdir,
+                                                   "-Wl,-rpath,/opt/rocm/lib"]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    return out
+
+
 def gpu_has_device():
     import ctypes
 

@@ -4,15 +4,16 @@
 //  * tables: every safe box has the final-pass property (every KD leaf whose closed cell meets it lists
 //    the slot's triangle — an independent recursive sweep, not scene_prepare's), every split value is a
 //    member of its axis' hash set, the load factor is <= 0.5 (shipped: <= 0.25), and -0 finds +0;
-//  * rays: the bounded traversal as the kernels run it — the s_min query, then the certificate, then
-//    (uncertified) the bounded KD descent — returns the plain KD traversal's triangle and barycentrics
+//  * rays: the bounded traversal as the kernels run it (restated in csrc/host/trace_host.h) — the s_min query,
+//    then the certificate, then (uncertified) the bounded KD descent, IEEE divisions, a T* entry that does
+//    not pass ending the program — returns the plain KD traversal's triangle and barycentrics
 //    bit for bit; a certified ray's descent is run too and must agree;
 //  * slack: for every ray whose hit point passes the box test, the shipped delta (rt_cert_delta) is at
 //    least 4x the derived bound e_P + delta_desc + the box comparison's own rounding, evaluated from
 //    the ray's actual magnitudes in double.
 //
-// Ray sets: the mix of wide_smin_check.cpp (camera rays, bounces off random triangles — some grazing,
-// some axis-parallel —, chords of transparent objects), rays whose origin coordinate IS a split value
+// Ray sets: the mix of wide_smin_check.cpp, from trace_host.h's ray makers (camera rays, bounces off random
+// triangles — some grazing, some axis-parallel —, chords of transparent objects), rays whose origin coordinate IS a split value
 // on an axis they go up / down (the reference's H5 quirk: t = 0 goes to the lower side), and rays aimed
 // at the extreme vertex of a triangle on a random axis (the hit point closest to a safe-box face).
 //
@@ -40,164 +41,11 @@
 #include <random>
 #include <vector>
 
-#include "bvh_common.h"
-#include "host/bvh_build.h"
-#include "host/rt_host.h"
+#include "host/trace_host.h"
+
+using namespace trace_host;
 
 namespace {
-
-float bitsf(uint32_t u)
-{
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-uint32_t fbits(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return u;
-}
-
-struct Hit {
-    int tri = -1;
-    float b[3] = {0, 0, 0};
-};
-
-bool scene_box(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float &t1, float &t2)
-{
-    const Bounding_Box &b = h.bounds;
-    float tminx = (b.min.x - o.x) / d.x, tminy = (b.min.y - o.y) / d.y, tminz = (b.min.z - o.z) / d.z;
-    float tmaxx = (b.max.x - o.x) / d.x, tmaxy = (b.max.y - o.y) / d.y, tmaxz = (b.max.z - o.z) / d.z;
-    t1 = fmaxf(fmaxf(fminf(tminx, tmaxx), fminf(tminy, tmaxy)), fminf(tminz, tmaxz));
-    t2 = fminf(fminf(fmaxf(tminx, tmaxx), fmaxf(tminy, tmaxy)), fmaxf(tminz, tmaxz));
-    return t1 <= t2;
-}
-
-// bvh_trace.h kd_bounded (s_min = -inf: trace_ray itself); tstar >= 0: a leaf listing T* tests its entry alone
-Hit kd_trace(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float entry, float exit_, float s_min, int tstar)
-{
-    Hit hit;
-    struct E { uint32_t node; float entry; } stk[64];
-    int sp = 0;
-    const float root_exit = exit_;
-    uint32_t node = 0;
-    while (true) {
-        uint32_t nx = h.nodes[2 * node], ny = h.nodes[2 * node + 1];
-        while ((ny & 3u) != RT_LEAF_TAG) {
-            const uint32_t axis = ny & 3u;
-            const float split = bitsf(nx);
-            const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
-            const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
-            uint32_t near_c = node + 1, far_c = ny >> 2;
-            if (oax >= split) std::swap(near_c, far_c);
-            const float t = (split - oax) / dax;
-            if (t >= exit_ || t < 0) {
-                node = near_c;
-            } else if (t <= entry) {
-                node = far_c;
-            } else if (t <= s_min) {
-                node = far_c;
-                entry = t;
-            } else {
-                stk[sp++] = E{far_c, t};
-                node = near_c;
-                exit_ = t;
-            }
-            nx = h.nodes[2 * node];
-            ny = h.nodes[2 * node + 1];
-        }
-        const uint32_t count = ny >> 2;
-        if (count > 0 && exit_ > s_min) {
-            float smallest = exit_;
-            uint32_t lo = nx, hi = nx + count;
-            if (tstar >= 0)
-                for (uint32_t e = nx; e < nx + count; ++e)
-                    if (h.isect_tri[e] == (uint32_t)tstar) {
-                        lo = e;
-                        hi = e + 1;
-                        break;
-                    }
-            for (uint32_t e = lo; e < hi; ++e) {
-                float s, b[3];
-                if (rt_tri_plane(h.isect_a[e], o, d, smallest, s) &&
-                    rt_tri_bary(h.isect_bary[e].b, h.isect_bary[e].c, h.isect_bary[e].d, bitsf(h.isect_bary[e].rd), o, d,
-                                s, b[0], b[1], b[2])) {
-                    smallest = s;
-                    hit.tri = (int)h.isect_bary[e].tri;
-                    memcpy(hit.b, b, sizeof b);
-                }
-            }
-            if (hit.tri >= 0) return hit;
-            if (hi - lo != count) {
-                fprintf(stderr, "T* entry of a leaf did not pass\n");
-                exit(3);
-            }
-        }
-        if (sp == 0) return hit;
-        --sp;
-        node = stk[sp].node;
-        entry = stk[sp].entry;
-        exit_ = sp > 0 ? stk[sp - 1].entry : root_exit;
-    }
-}
-
-// the s_min query (bvh_trace.h bvh4_query): nearest child first, best lowered test by test; tk as leaf_scan_min
-float seq_query(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float best, int &tk)
-{
-    tk = -1;
-    const RtSlab sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, h.bvh_scale));
-    struct E { uint32_t ref; float tn; };
-    std::vector<E> stk;
-    uint32_t cur = 0;
-    auto pop = [&]() -> uint32_t {
-        while (!stk.empty()) {
-            const E e = stk.back();
-            stk.pop_back();
-            if (e.tn <= best) return e.ref;
-        }
-        return RT_BVH_EMPTY;
-    };
-    while (true) {
-        while (!(cur & RT_BVH_LEAF)) {
-            const float *f = reinterpret_cast<const float *>(&h.bvh4[8 * (size_t)cur]);
-            const uint32_t *rf = reinterpret_cast<const uint32_t *>(f + 24);
-            E c[4];
-            for (int k = 0; k < 4; ++k) {
-                float tn;
-                const bool hit = rt_bvh_box(f[k], f[4 + k], f[8 + k], f[12 + k], f[16 + k], f[20 + k], sl, best, tn) &&
-                                 rf[k] != RT_BVH_EMPTY;
-                c[k] = hit ? E{rf[k], tn} : E{RT_BVH_EMPTY, INFINITY};
-            }
-            std::stable_sort(c, c + 4, [](const E &a, const E &b) {
-                const bool ea = a.ref == RT_BVH_EMPTY, eb = b.ref == RT_BVH_EMPTY;
-                return ea != eb ? eb : a.tn < b.tn;
-            });
-            for (int k = 3; k >= 1; --k)
-                if (c[k].ref != RT_BVH_EMPTY) stk.push_back(c[k]);
-            cur = c[0].ref != RT_BVH_EMPTY ? c[0].ref : pop();
-        }
-        if (cur == RT_BVH_EMPTY) break;
-        const uint32_t first = (cur & ~RT_BVH_LEAF) >> 3, end = first + (cur & 7u) + 1u;
-        for (uint32_t e = first; e < end; ++e) {
-            float s, b[3];
-            if (!rt_tri_plane(h.bvh_a[e], o, d, INFINITY, s) || !(s <= best)) continue;
-            const bool lt = s < best;
-            if (!lt && tk < 0) continue;
-            const RtIsectBary &R = h.bvh_bary[e];
-            if (!rt_tri_bary(R.b, R.c, R.d, bitsf(R.rd), o, d, s, b[0], b[1], b[2])) continue;
-            if (lt) {
-                best = s;
-                tk = (int)e;
-            } else {
-                tk = -2; // RT_TK_TIE
-            }
-        }
-        cur = pop();
-        if (cur == RT_BVH_EMPTY) break;
-    }
-    return best;
-}
 
 // ---- the tables
 // leaves whose closed cell meets [blo, bhi] and that do not list triangle t (recursive, on its own)
@@ -268,8 +116,6 @@ struct Tally {
     }
 };
 
-bool same(const Hit &a, const Hit &b) { return a.tri == b.tri && memcmp(a.b, b.b, sizeof a.b) == 0; }
-
 struct Last { // what the certificate said about the last ray (why < 0: it was never asked)
     int why = -1, tk = -1;
     float s_min = 0.0f;
@@ -282,10 +128,11 @@ void check_ray(const rt_host::PreparedHost &h, const RtKdCert &kc, Vec3D o, Vec3
     if (!scene_box(h, o, d, t1, t2)) return;
     if (!rt_bounded_ray(o, d, h.split_vals.data(), h.split_off)) return;
     ++t.bounded;
-    const Hit plain = kd_trace(h, o, d, t1, t2, -INFINITY, -1);
+    const Hit plain = kd_plain(h, o, d, t1, t2);
     if (plain.tri >= 0) ++t.hits;
-    int tk;
-    const float s_min = seq_query(h, o, d, t2, tk);
+    const Smin q = bvh4_smin(h, o, d, t2);
+    const float s_min = q.best;
+    const int tk = q.tk;
     Hit got;
     if (s_min < t2) { // (else: a miss, as trace_bvh returns it)
         const int why = rt_kd_cert(kc, o, d, t1, t2, s_min, tk);
@@ -300,12 +147,12 @@ void check_ray(const rt_host::PreparedHost &h, const RtKdCert &kc, Vec3D o, Vec3
             ++t.on_split_up;
             if (why == RT_CERT_OK) ++t.on_split_up_cert; // (must stay 0: the hash sets' job)
         }
-        const Hit desc = kd_trace(h, o, d, t1, t2, s_min, tk >= 0 ? (int)h.bvh_bary[tk].tri : -1);
+        const Hit desc = kd_descent<IEEE_DIV, HARD_FAILURE>(h, o, d, t1, t2, s_min, tstar_of(h, tk));
         if (why == RT_CERT_OK) {
             ++t.certified;
             const RtIsectBary &R = h.bvh_bary[tk];
             if (rt_tri_bary(R.b, R.c, R.d, bitsf(R.rd), o, d, s_min, got.b[0], got.b[1], got.b[2])) got.tri = (int)R.tri;
-            if (!same(got, desc)) ++t.cert_descent_mism;
+            if (!same_hit(got, desc)) ++t.cert_descent_mism;
         } else {
             got = desc;
         }
@@ -324,7 +171,7 @@ void check_ray(const rt_host::PreparedHost &h, const RtKdCert &kc, Vec3D o, Vec3
             }
         }
     }
-    if (!same(got, plain)) {
+    if (!same_hit(got, plain)) {
         if (++t.mism <= 3)
             fprintf(stderr, "MISMATCH o (%a %a %a) d (%a %a %a): kd %d, certificate path %d (tk %d)\n", o.x, o.y, o.z, d.x,
                     d.y, d.z, plain.tri, got.tri, tk);
@@ -347,16 +194,8 @@ int report(const Tally &t)
 // `file`: the rays of a raw float32 (n, 6) file
 int run_file(const rt_host::PreparedHost &h, const char *path)
 {
-    FILE *f = fopen(path, "rb");
-    if (!f) {
-        fprintf(stderr, "cannot open %s\n", path);
-        return 2;
-    }
     std::vector<float> v;
-    float buf[6 * 4096];
-    size_t got;
-    while ((got = fread(buf, sizeof(float), 6 * 4096, f)) > 0) v.insert(v.end(), buf, buf + got);
-    fclose(f);
+    if (!read_rays_f32(path, v)) return 2;
     const long long n = (long long)(v.size() / 6);
     const RtKdCert kc = h.kd_cert();
     Tally total;
@@ -365,9 +204,8 @@ int run_file(const rt_host::PreparedHost &h, const char *path)
         Tally t;
 #pragma omp for schedule(dynamic, 1024)
         for (long long k = 0; k < n; ++k) {
-            const float *r = &v[6 * (size_t)k];
             ++t.rays;
-            check_ray(h, kc, rt_v3(r[0], r[1], r[2]), rt_v3(r[3], r[4], r[5]), t);
+            check_ray(h, kc, ray_o(v, (size_t)k), ray_d(v, (size_t)k), t);
         }
 #pragma omp critical
         total.add(t);
@@ -479,25 +317,13 @@ int main(int argc, char **argv)
     }
     RtHostScene scene;
     Camera cam;
-    if (rt_host::load_scene_file(scene, argv[1], &cam) != RT_OK) {
-        fprintf(stderr, "scene load failed\n");
-        return 2;
-    }
-    const int n = (int)scene.tris.size();
-    std::vector<KD_Tree_Node> nodes;
-    std::vector<int> indices;
-    Bounding_Box bounds;
-    if (rt_host::build_kd_tree(scene.tris.data(), n, nodes, indices, bounds) != RT_OK) return 2;
-    std::vector<int> lights = rt_host::light_list(scene.tris.data(), n);
     rt_host::PreparedHost h;
-    const double t0 = omp_get_wtime();
-    if (rt_host::prepare_host(scene.tris.data(), n, nodes.data(), (int)nodes.size(), indices.data(),
-                              (int)indices.size(), lights.data(), (int)lights.size(), bounds, h) != RT_OK ||
-        h.bvh_depth < 0 || h.kd_safe.empty()) {
+    double t_prep = 0;
+    if (!load_prepared(argv[1], scene, cam, h, &t_prep) || h.bvh_depth < 0 || h.kd_safe.empty()) {
         fprintf(stderr, "prepare failed / no BVH or certificate tables built\n");
         return 2;
     }
-    const double t_prep = omp_get_wtime() - t0;
+    const int n = (int)scene.tris.size();
     long long nonempty = 0;
     const int tc = check_tables(h, nonempty);
     printf("tris %d slots %zu safe boxes %lld prepare %.3f s cert bytes %zu tables %d\n", n, h.bvh_bary.size(), nonempty,
@@ -523,21 +349,9 @@ int main(int argc, char **argv)
         Tally t;
         std::mt19937_64 rng(seed + 0x9e3779b97f4a7c15ull * (unsigned)(omp_get_thread_num() + 1));
         std::uniform_real_distribution<float> U(0.0f, 1.0f);
-        auto unit = [&]() {
-            while (true) {
-                Vec3D v = rt_v3(2 * U(rng) - 1, 2 * U(rng) - 1, 2 * U(rng) - 1);
-                const float l = rt_dot(v, v);
-                if (l > 1e-6f && l <= 1.0f) return rt_normalize(v);
-            }
-        };
-        auto on_tri = [&](const Triangle &tr) {
-            float b1 = U(rng), b2 = U(rng);
-            if (b1 + b2 > 1) {
-                b1 = 1 - b1;
-                b2 = 1 - b2;
-            }
-            return tr.p1 + b1 * (tr.p2 - tr.p1) + b2 * (tr.p3 - tr.p1);
-        };
+        auto u = [&]() { return U(rng); };
+        auto unit = [&]() { return unit_vector(u); };
+        auto on_tri = [&](const Triangle &tr) { return point_on(tr, u); };
         auto rand_tri = [&]() -> const Triangle & { return scene.tris[(size_t)(U(rng) * n) % n]; };
 #pragma omp for schedule(dynamic, 1024)
         for (long long k = 0; k < rays; ++k) {
@@ -574,25 +388,13 @@ int main(int argc, char **argv)
                 o = on_tri(rand_tri());
                 d = rt_normalize(target - o);
             } else if (mode >= 4 && !glass.empty()) {
-                const size_t gi = (size_t)(U(rng) * glass.size()) % glass.size();
-                const Triangle &tr = scene.tris[(size_t)glass[gi]];
-                o = on_tri(tr);
-                const long long span = mode == 4 ? (long long)glass.size() : 64;
-                const long long gj = (long long)gi + (long long)((U(rng) - 0.5f) * span);
-                const Triangle &to = scene.tris[(size_t)glass[(size_t)((gj % (long long)glass.size() + glass.size()) % glass.size())]];
-                d = rt_normalize(on_tri(to) - o);
+                (void)glass_chord(scene, glass, mode == 4 ? (long long)glass.size() : 64, u, o, d);
             } else { // a bounce: from a point on a random triangle, some grazing / axis-parallel
                 const Triangle &tr = rand_tri();
                 o = on_tri(tr);
                 d = unit();
-                if (mode == 2) {
-                    const Vec3D nn = rt_normalize(rt_cross(tr.p2 - tr.p1, tr.p3 - tr.p1));
-                    if (nn.x == nn.x) d = rt_normalize(d - rt_dot(d, nn) * nn + 1e-4f * (U(rng) - 0.5f) * nn);
-                } else if (mode == 3 && (k & 8)) {
-                    const int a = (int)(k >> 4) % 3;
-                    if (a == 0) d.x = 0; else if (a == 1) d.y = 0; else d.z = 0;
-                    d = rt_normalize(d);
-                }
+                if (mode == 2) d = grazing(d, tr, u);
+                else if (mode == 3 && (k & 8)) d = axis_parallel(d, (int)(k >> 4) % 3);
             }
             ++t.rays;
             if (d.x != d.x || d.y != d.y || d.z != d.z) continue; // (a degenerate aim: no ray)

@@ -7,7 +7,7 @@
 //    exactly once, and every child box a bit copy of the box the binary tree
 //    stores for the node over the same set of leaves;
 //  * the query: (best, tk) equal to the sequential 4-wide query's (bvh_trace.h
-//    bvh4_query: depth-first, best lowered test by test) bit for bit, with its
+//    bvh4_query, restated in csrc/host/trace_host.h bvh4_smin: depth-first, best lowered test by test) bit for bit, with its
 //    lists walked forwards and backwards, for camera rays, bounce rays (some
 //    grazing, some axis-parallel), chords through the transparent objects at
 //    total-internal-reflection angles and grazing chords;
@@ -33,161 +33,9 @@
 
 #include "host/wide_smin_host.h"
 
+using namespace trace_host;
+
 namespace {
-
-float bitsf(uint32_t u)
-{
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-uint32_t fbits(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return u;
-}
-
-struct Hit {
-    int tri = -1;
-    float b[3] = {0, 0, 0};
-};
-
-bool scene_box(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float &t1, float &t2)
-{
-    const Bounding_Box &b = h.bounds;
-    float tminx = (b.min.x - o.x) / d.x, tminy = (b.min.y - o.y) / d.y, tminz = (b.min.z - o.z) / d.z;
-    float tmaxx = (b.max.x - o.x) / d.x, tmaxy = (b.max.y - o.y) / d.y, tmaxz = (b.max.z - o.z) / d.z;
-    t1 = fmaxf(fmaxf(fminf(tminx, tmaxx), fminf(tminy, tmaxy)), fminf(tminz, tmaxz));
-    t2 = fminf(fminf(fmaxf(tminx, tmaxx), fmaxf(tminy, tmaxy)), fmaxf(tminz, tmaxz));
-    return t1 <= t2;
-}
-
-// bvh_trace.h kd_bounded (s_min = -inf: trace_ray itself); tstar >= 0: a leaf listing T* tests its entry alone
-Hit kd_trace(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float entry, float exit_, float s_min, int tstar)
-{
-    Hit hit;
-    struct E { uint32_t node; float entry; } stk[64];
-    int sp = 0;
-    const float root_exit = exit_;
-    uint32_t node = 0;
-    while (true) {
-        uint32_t nx = h.nodes[2 * node], ny = h.nodes[2 * node + 1];
-        while ((ny & 3u) != RT_LEAF_TAG) {
-            const uint32_t axis = ny & 3u;
-            const float split = bitsf(nx);
-            const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
-            const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
-            uint32_t near_c = node + 1, far_c = ny >> 2;
-            if (oax >= split) std::swap(near_c, far_c);
-            const float t = (split - oax) / dax;
-            if (t >= exit_ || t < 0) {
-                node = near_c;
-            } else if (t <= entry) {
-                node = far_c;
-            } else if (t <= s_min) {
-                node = far_c;
-                entry = t;
-            } else {
-                stk[sp++] = E{far_c, t};
-                node = near_c;
-                exit_ = t;
-            }
-            nx = h.nodes[2 * node];
-            ny = h.nodes[2 * node + 1];
-        }
-        const uint32_t count = ny >> 2;
-        if (count > 0 && exit_ > s_min) {
-            float smallest = exit_;
-            uint32_t lo = nx, hi = nx + count;
-            if (tstar >= 0)
-                for (uint32_t e = nx; e < nx + count; ++e)
-                    if (h.isect_tri[e] == (uint32_t)tstar) {
-                        lo = e;
-                        hi = e + 1;
-                        break;
-                    }
-            for (uint32_t e = lo; e < hi; ++e) {
-                float s, b[3];
-                if (rt_tri_plane(h.isect_a[e], o, d, smallest, s) &&
-                    rt_tri_bary(h.isect_bary[e].b, h.isect_bary[e].c, h.isect_bary[e].d, bitsf(h.isect_bary[e].rd), o, d,
-                                s, b[0], b[1], b[2])) {
-                    smallest = s;
-                    hit.tri = (int)h.isect_bary[e].tri;
-                    memcpy(hit.b, b, sizeof b);
-                }
-            }
-            if (hit.tri >= 0) return hit;
-            if (hi - lo != count) {
-                fprintf(stderr, "T* entry of a leaf did not pass\n");
-                exit(3);
-            }
-        }
-        if (sp == 0) return hit;
-        --sp;
-        node = stk[sp].node;
-        entry = stk[sp].entry;
-        exit_ = sp > 0 ? stk[sp - 1].entry : root_exit;
-    }
-}
-
-// the sequential query (bvh_trace.h bvh4_query on the 4-wide collapse): nearest child first, the
-// others pushed farthest-first, best lowered test by test; tk as leaf_scan_min keeps it
-float seq_query(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float best, int &tk)
-{
-    tk = -1;
-    const RtSlab sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, h.bvh_scale));
-    struct E { uint32_t ref; float tn; };
-    std::vector<E> stk;
-    uint32_t cur = 0;
-    auto pop = [&]() -> uint32_t {
-        while (!stk.empty()) {
-            const E e = stk.back();
-            stk.pop_back();
-            if (e.tn <= best) return e.ref;
-        }
-        return RT_BVH_EMPTY;
-    };
-    while (true) {
-        while (!(cur & RT_BVH_LEAF)) {
-            const float *f = reinterpret_cast<const float *>(&h.bvh4[8 * (size_t)cur]);
-            const uint32_t *rf = reinterpret_cast<const uint32_t *>(f + 24);
-            E c[4];
-            for (int k = 0; k < 4; ++k) {
-                float tn;
-                const bool hit = rt_bvh_box(f[k], f[4 + k], f[8 + k], f[12 + k], f[16 + k], f[20 + k], sl, best, tn) &&
-                                 rf[k] != RT_BVH_EMPTY;
-                c[k] = hit ? E{rf[k], tn} : E{RT_BVH_EMPTY, INFINITY};
-            }
-            std::stable_sort(c, c + 4, [](const E &a, const E &b) {
-                const bool ea = a.ref == RT_BVH_EMPTY, eb = b.ref == RT_BVH_EMPTY;
-                return ea != eb ? eb : a.tn < b.tn;
-            });
-            for (int k = 3; k >= 1; --k)
-                if (c[k].ref != RT_BVH_EMPTY) stk.push_back(c[k]);
-            cur = c[0].ref != RT_BVH_EMPTY ? c[0].ref : pop();
-        }
-        if (cur == RT_BVH_EMPTY) break;
-        const uint32_t first = (cur & ~RT_BVH_LEAF) >> 3, end = first + (cur & 7u) + 1u;
-        for (uint32_t e = first; e < end; ++e) {
-            float s, b[3];
-            if (!rt_tri_plane(h.bvh_a[e], o, d, INFINITY, s) || !(s <= best)) continue;
-            const bool lt = s < best;
-            if (!lt && tk < 0) continue;
-            const RtIsectBary &R = h.bvh_bary[e];
-            if (!rt_tri_bary(R.b, R.c, R.d, bitsf(R.rd), o, d, s, b[0], b[1], b[2])) continue;
-            if (lt) {
-                best = s;
-                tk = (int)e;
-            } else {
-                tk = WSM_TK_TIE;
-            }
-        }
-        cur = pop();
-        if (cur == RT_BVH_EMPTY) break;
-    }
-    return best;
-}
 
 // ---- structure: the wide tree against the binary tree
 struct BoxBits {
@@ -325,8 +173,10 @@ void check_ray(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, Tally &t)
     if (!(o.x - o.x == 0.0f && o.y - o.y == 0.0f && o.z - o.z == 0.0f && d.x - d.x == 0.0f && d.y - d.y == 0.0f &&
           d.z - d.z == 0.0f) || !(fabsf(o.x) + fabsf(o.y) + fabsf(o.z) < 0x1p64f))
         return;
-    int tk_seq, tk_a = -1, tk_b = -1;
-    const float s_seq = seq_query(h, o, d, t2, tk_seq);
+    int tk_a = -1, tk_b = -1;
+    const Smin seq = bvh4_smin(h, o, d, t2); // the sequential query (bvh_trace.h bvh4_query)
+    const float s_seq = seq.best;
+    const int tk_seq = seq.tk;
     float s_a = 0, s_b = 0;
     WsmWork wa, wb;
     const bool ok_a = wide_smin_host(h.bvh_wide, RT_BVHW_ARITY, h, o, d, t2, kFcap, kLcap, false, s_a, tk_a, wa);
@@ -344,7 +194,7 @@ void check_ray(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, Tally &t)
         t.tests += wa.tests;
         t.frontier = wa.frontier > t.frontier ? wa.frontier : t.frontier;
         t.leaves = wa.leaves > t.leaves ? wa.leaves : t.leaves;
-        if (tk_a == WSM_TK_TIE) {
+        if (tk_a == TK_TIE) {
             ++t.ties;
             if (wa.cross_round || wb.cross_round) ++t.cross_ties;
         }
@@ -352,27 +202,27 @@ void check_ray(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, Tally &t)
     // the whole bounce as wf_long runs it, against the plain KD traversal
     if (!rt_bounded_ray(o, d, h.split_vals.data(), h.split_off)) return;
     ++t.bounded;
-    const Hit plain = kd_trace(h, o, d, t1, t2, -INFINITY, -1);
+    const Hit plain = kd_plain(h, o, d, t1, t2);
     if (plain.tri >= 0) ++t.hits;
     auto bounce = [&](size_t fcap, size_t lcap, bool &fell_back) {
         float s_min;
         int tk;
         WsmWork w;
         fell_back = !wide_smin_host(h.bvh_wide, RT_BVHW_ARITY, h, o, d, t2, fcap, lcap, false, s_min, tk, w);
-        if (fell_back) return kd_trace(h, o, d, t1, t2, -INFINITY, -1); // (the wide KD traversal: trace_ray's result)
+        if (fell_back) return kd_plain(h, o, d, t1, t2); // (the wide KD traversal: trace_ray's result)
         if (!(s_min < t2)) return Hit{};
-        return kd_trace(h, o, d, t1, t2, s_min, tk >= 0 ? (int)h.bvh_bary[tk].tri : -1);
+        return kd_descent<IEEE_DIV, HARD_FAILURE>(h, o, d, t1, t2, s_min, tstar_of(h, tk));
     };
     bool fb = false;
     const Hit a = bounce(kFcap, kLcap, fb);
-    if (a.tri != plain.tri || memcmp(a.b, plain.b, sizeof a.b) != 0) {
+    if (!same_hit(a, plain)) {
         if (++t.hit_mism <= 3)
             fprintf(stderr, "HIT MISMATCH o (%a %a %a) d (%a %a %a): kd %d, wide bounded %d\n", o.x, o.y, o.z, d.x, d.y,
                     d.z, plain.tri, a.tri);
     }
     const Hit f = bounce(1, 1, fb); // the forced fallback
     if (fb) ++t.forced;
-    if (f.tri != plain.tri || memcmp(f.b, plain.b, sizeof f.b) != 0) ++t.fallback_mism;
+    if (!same_hit(f, plain)) ++t.fallback_mism;
 }
 
 int report(const Tally &t, bool need_forced)
@@ -400,23 +250,12 @@ int main(int argc, char **argv)
     }
     RtHostScene scene;
     Camera cam;
-    if (rt_host::load_scene_file(scene, argv[1], &cam) != RT_OK) {
-        fprintf(stderr, "scene load failed\n");
-        return 2;
-    }
-    const int n = (int)scene.tris.size();
-    std::vector<KD_Tree_Node> nodes;
-    std::vector<int> indices;
-    Bounding_Box bounds;
-    if (rt_host::build_kd_tree(scene.tris.data(), n, nodes, indices, bounds) != RT_OK) return 2;
-    std::vector<int> lights = rt_host::light_list(scene.tris.data(), n);
     rt_host::PreparedHost h;
-    if (rt_host::prepare_host(scene.tris.data(), n, nodes.data(), (int)nodes.size(), indices.data(),
-                              (int)indices.size(), lights.data(), (int)lights.size(), bounds, h) != RT_OK ||
-        h.bvh_depth < 0) {
+    if (!load_prepared(argv[1], scene, cam, h) || h.bvh_depth < 0) {
         fprintf(stderr, "prepare failed / no BVH built\n");
         return 2;
     }
+    const int n = (int)scene.tris.size();
     const int sc = check_structure(h, h.bvh_wide, RT_BVHW_ARITY);
     printf("tris %d bvh_nodes %zu wide nodes %zu (arity %d) structure %d\n", n, h.bvh_nodes.size() / 4,
            h.bvh_wide.size() / (2 * RT_BVHW_ARITY), RT_BVHW_ARITY, sc);
@@ -462,55 +301,25 @@ int main(int argc, char **argv)
         Tally t;
         std::mt19937_64 rng(seed + 0x9e3779b97f4a7c15ull * (unsigned)(omp_get_thread_num() + 1));
         std::uniform_real_distribution<float> U(0.0f, 1.0f);
-        auto unit = [&]() {
-            while (true) {
-                Vec3D v = rt_v3(2 * U(rng) - 1, 2 * U(rng) - 1, 2 * U(rng) - 1);
-                const float l = rt_dot(v, v);
-                if (l > 1e-6f && l <= 1.0f) return rt_normalize(v);
-            }
-        };
-        auto on_tri = [&](const Triangle &tr) {
-            float b1 = U(rng), b2 = U(rng);
-            if (b1 + b2 > 1) {
-                b1 = 1 - b1;
-                b2 = 1 - b2;
-            }
-            return tr.p1 + b1 * (tr.p2 - tr.p1) + b2 * (tr.p3 - tr.p1);
-        };
+        auto u = [&]() { return U(rng); };
 #pragma omp for schedule(dynamic, 1024)
         for (long long k = 0; k < rays; ++k) {
             Vec3D o, d;
             const int mode = (int)(k % 6);
             if (mode == 0) { // from the camera
                 o = cam.position;
-                d = unit();
+                d = unit_vector(u);
             } else if (mode >= 4 && !glass.empty()) {
                 // a chord of a transparent object: from a point of its surface towards a point of a triangle
                 // near it in the mesh's order (mode 4), or nearly along the surface (mode 5: grazing)
-                const size_t gi = (size_t)(U(rng) * glass.size()) % glass.size();
-                const Triangle &tr = scene.tris[(size_t)glass[gi]];
-                o = on_tri(tr);
-                const long long span = mode == 4 ? (long long)glass.size() : 64;
-                const long long gj = (long long)gi + (long long)((U(rng) - 0.5f) * span);
-                const Triangle &to = scene.tris[(size_t)glass[(size_t)((gj % (long long)glass.size() + glass.size()) % glass.size())]];
-                d = rt_normalize(on_tri(to) - o);
-                if (mode == 5) {
-                    const Vec3D nn = rt_normalize(rt_cross(tr.p2 - tr.p1, tr.p3 - tr.p1));
-                    const Vec3D u = unit();
-                    if (nn.x == nn.x) d = rt_normalize(u - rt_dot(u, nn) * nn + (0.02f + 0.18f * U(rng)) * (rt_dot(d, nn) < 0 ? -1.0f : 1.0f) * nn);
-                }
+                const Triangle &tr = glass_chord(scene, glass, mode == 4 ? (long long)glass.size() : 64, u, o, d);
+                if (mode == 5) d = grazing_chord(d, tr, u);
             } else { // a bounce: from a point on a random triangle, some grazing / axis-parallel
-                const Triangle &tr = scene.tris[(size_t)(U(rng) * n) % n];
-                o = on_tri(tr);
-                d = unit();
-                if (mode == 2) {
-                    const Vec3D nn = rt_normalize(rt_cross(tr.p2 - tr.p1, tr.p3 - tr.p1));
-                    if (nn.x == nn.x) d = rt_normalize(d - rt_dot(d, nn) * nn + 1e-4f * (U(rng) - 0.5f) * nn);
-                } else if (mode == 3 && (k & 8)) {
-                    const int a = (int)(k >> 4) % 3;
-                    if (a == 0) d.x = 0; else if (a == 1) d.y = 0; else d.z = 0;
-                    d = rt_normalize(d);
-                }
+                const Triangle &tr = scene.tris[(size_t)(u() * n) % n];
+                o = point_on(tr, u);
+                d = unit_vector(u);
+                if (mode == 2) d = grazing(d, tr, u);
+                else if (mode == 3 && (k & 8)) d = axis_parallel(d, (int)(k >> 4) % 3);
             }
             if (d.x != d.x) continue;
             check_ray(h, o, d, t);

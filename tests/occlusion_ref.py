@@ -17,15 +17,10 @@ import subprocess
 
 import numpy as np
 
+import helpers
 import independent as ind
-import rt
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "isaklm-raytracer_amd", "csrc")
-INC = os.path.join(ROOT, "include")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I" + INC, "-I" + CSRC]
 THRESHOLD_KINDS = ("inbox", "outside", "gate:4")  # the ray sets of the bit-exact threshold tests
 
 
@@ -46,13 +41,7 @@ def s_reference(tris, rays, tri):
 
 def build_checker(outdir):
     """compiles tests/native/occlusion_check.cpp against the built library; returns the binary's path"""
-    rt.lib()  # the library must exist (and match the header)
-    out = os.path.join(str(outdir), "occlusion_check")
-    libdir = os.path.dirname(rt.LIB_PATH)
-    cmd = ["g++"] + FLAGS + [os.path.join(NATIVE, "occlusion_check.cpp"), "-o", out, "-L" + libdir, "-lisaklm_rt",
-                             "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return out
+    return helpers.build_native(outdir, "occlusion_check", openmp=False)
 
 
 DUMP = np.dtype([("hit", "<i4"), ("triangle", "<i4"), ("s", "<f4")])

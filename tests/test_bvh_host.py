@@ -23,34 +23,16 @@ import pytest
 import hazards
 import helpers
 import oracle
-import rt
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "isaklm-raytracer_amd", "csrc")
-INC = os.path.join(ROOT, "include")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I" + INC, "-I" + CSRC]
-
-
-def _build(tmp_path_factory, name, link_lib):
-    out = str(tmp_path_factory.mktemp("bvh") / name)
-    cmd = ["g++"] + FLAGS + [os.path.join(NATIVE, name + ".cpp"), "-o", out]
-    if link_lib:
-        libdir = os.path.dirname(rt.LIB_PATH)
-        cmd += ["-fopenmp", "-L" + libdir, "-lisaklm_rt", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return out
 
 
 @pytest.fixture(scope="module")
 def margin_check(tmp_path_factory):
-    return _build(tmp_path_factory, "bvh_margin_check", False)
+    return helpers.build_native(tmp_path_factory.mktemp("bvh"), "bvh_margin_check", link_lib=False)
 
 
 @pytest.fixture(scope="module")
 def trace_check(tmp_path_factory):
-    rt.lib()  # the library must exist (and match the header)
-    return _build(tmp_path_factory, "bvh_trace_check", True)
+    return helpers.build_native(tmp_path_factory.mktemp("bvh"), "bvh_trace_check")
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])

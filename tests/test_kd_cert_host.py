@@ -49,25 +49,13 @@ import pytest
 import hazards
 import helpers
 import oracle
-import rt
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "isaklm-raytracer_amd", "csrc")
-INC = os.path.join(ROOT, "include")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I" + INC, "-I" + CSRC]
 FLOORS = {"cornell": 0.35, "room_small": 0.46}
 
 
 @pytest.fixture(scope="module")
 def cert_check(tmp_path_factory):
-    rt.lib()  # the library must exist (and match the header)
-    out = str(tmp_path_factory.mktemp("kdc") / "kd_cert_check")
-    libdir = os.path.dirname(rt.LIB_PATH)
-    cmd = ["g++"] + FLAGS + [os.path.join(NATIVE, "kd_cert_check.cpp"), "-o", out, "-fopenmp", "-L" + libdir,
-                             "-lisaklm_rt", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return out
+    return helpers.build_native(tmp_path_factory.mktemp("kdc"), "kd_cert_check")
 
 
 def _field(out, name):

@@ -31,7 +31,7 @@ E_INVALID = -1
 
 
 def test_abi_version_and_signature():
-    text = open(os.path.join(oref.INC, "isaklm_rt.h")).read()
+    text = open(os.path.join(helpers.ROOT, "include", "isaklm_rt.h")).read()
     assert int(re.search(r"#define RT_ABI_VERSION (\d+)", text).group(1)) == 12
     assert rt.ABI_VERSION == 12 and rt.lib().rt_abi_version() == 12
     m = re.search(r"int rt_occluded\(([^;]*)\);", text)

@@ -18,11 +18,7 @@ import helpers
 import oracle
 import rt
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "isaklm-raytracer_amd", "csrc")
-INC = os.path.join(ROOT, "include")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I" + INC, "-I" + CSRC]
+INC = os.path.join(helpers.ROOT, "include")
 E_INVALID = -1
 
 
@@ -90,13 +86,7 @@ def test_argument_errors_without_a_device():
 # ---- the gate's domain on the host restatement ----
 @pytest.fixture(scope="module")
 def trace_check(tmp_path_factory):
-    rt.lib()  # the library must exist (and match the header)
-    out = str(tmp_path_factory.mktemp("query") / "bvh_trace_check")
-    libdir = os.path.dirname(rt.LIB_PATH)
-    cmd = ["g++"] + FLAGS + [os.path.join(NATIVE, "bvh_trace_check.cpp"), "-o", out, "-fopenmp", "-L" + libdir,
-                             "-lisaklm_rt", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return out
+    return helpers.build_native(tmp_path_factory.mktemp("query"), "bvh_trace_check")
 
 
 def _rescaled(g, unit, target):

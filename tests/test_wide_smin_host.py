@@ -24,24 +24,11 @@ import pytest
 import hazards
 import helpers
 import oracle
-import rt
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "isaklm-raytracer_amd", "csrc")
-INC = os.path.join(ROOT, "include")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I" + INC, "-I" + CSRC]
 
 
 @pytest.fixture(scope="module")
 def smin_check(tmp_path_factory):
-    rt.lib()  # the library must exist (and match the header)
-    out = str(tmp_path_factory.mktemp("wsm") / "wide_smin_check")
-    libdir = os.path.dirname(rt.LIB_PATH)
-    cmd = ["g++"] + FLAGS + [os.path.join(NATIVE, "wide_smin_check.cpp"), "-o", out, "-fopenmp", "-L" + libdir,
-                             "-lisaklm_rt", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.run(cmd, check=True, capture_output=True, text=True)
-    return out
+    return helpers.build_native(tmp_path_factory.mktemp("wsm"), "wide_smin_check")
 
 
 def _run(exe, scene, rays=200_000, seed=7, cam=None, edges=False):
