@@ -134,6 +134,21 @@ __device__ __forceinline__ void leaf_scan_min(const RtF4 *plane, const RtIsectBa
     }
 }
 
+// the s_min queries' pop: the next stacked subtree that may still hold a smaller s — entered at
+// tn <= best — (RT_BVH_EMPTY: none)
+template <typename STACK>
+__device__ __forceinline__ uint32_t bvh_pop(STACK &stk, int &sp, const float best)
+{
+    while (sp > 0) {
+        --sp;
+        uint32_t n;
+        float tn;
+        stk.get(sp, n, tn);
+        if (tn <= best) return n;
+    }
+    return RT_BVH_EMPTY;
+}
+
 // s_min of step 2: the smallest s < best of any passing test (best if none)
 template <bool COUNT, typename STACK>
 __device__ __forceinline__ float bvh_bound(const RtDevScene &sc, Vec3D o, Vec3D d, float best, STACK &stk, Cnt &cn)
@@ -141,17 +156,6 @@ __device__ __forceinline__ float bvh_bound(const RtDevScene &sc, Vec3D o, Vec3D 
     const RtSlab sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, sc.bvh_scale));
     int sp = 0;
     uint32_t cur = 0; // the root (always an inner node)
-    // pop the next subtree that may still hold a smaller s (RT_BVH_EMPTY: none)
-    auto pop = [&]() -> uint32_t {
-        while (sp > 0) {
-            --sp;
-            uint32_t n;
-            float tn;
-            stk.get(sp, n, tn);
-            if (tn <= best) return n;
-        }
-        return RT_BVH_EMPTY;
-    };
     // "while-while" (SIMT): the lanes descend inner nodes together until each
     // holds a leaf (or is done), then test their leaves together — a lane at a
     // leaf does not drag its wave through every other lane's node steps one
@@ -173,7 +177,7 @@ __device__ __forceinline__ float bvh_bound(const RtDevScene &sc, Vec3D o, Vec3D 
             } else if (h0 || h1) {
                 cur = h0 ? ch.x : ch.y;
             } else {
-                cur = pop();
+                cur = bvh_pop(stk, sp, best);
             }
         }
         if (cur == RT_BVH_EMPTY) return best;
@@ -181,7 +185,7 @@ __device__ __forceinline__ float bvh_bound(const RtDevScene &sc, Vec3D o, Vec3D 
         if (COUNT) cn.v[RT_CNT_B_BVH_TRI] += end - first;
         float bx, by, bz;
         (void)leaf_scan<COUNT>(sc.bvh_a, sc.bvh_bary, first, end, o, d, best, bx, by, bz, cn);
-        cur = pop();
+        cur = bvh_pop(stk, sp, best);
         if (cur == RT_BVH_EMPTY) return best;
     }
 }
@@ -275,16 +279,6 @@ __device__ __forceinline__ bool bvh4_query(const RtDevScene &sc, Vec3D o, Vec3D 
         tk = pk.tk;
     }
     int steps = 0;
-    auto pop = [&]() -> uint32_t {
-        while (sp > 0) {
-            --sp;
-            uint32_t n;
-            float tn;
-            stk.get(sp, n, tn);
-            if (tn <= best) return n;
-        }
-        return RT_BVH_EMPTY;
-    };
     while (true) {
         while (!(cur & RT_BVH_LEAF)) {
             if (PARK) {
@@ -299,13 +293,13 @@ __device__ __forceinline__ bool bvh4_query(const RtDevScene &sc, Vec3D o, Vec3D 
             }
             if (COUNT) cn.v[RT_CNT_B_BVH_NODE]++;
             const uint32_t next = bvh4_children(sc, cur, sl, best, stk, sp);
-            cur = next != RT_BVH_EMPTY ? next : pop();
+            cur = next != RT_BVH_EMPTY ? next : bvh_pop(stk, sp, best);
         }
         if (cur == RT_BVH_EMPTY) break;
         const uint32_t first = (cur & ~RT_BVH_LEAF) >> 3, end = first + (cur & 7u) + 1u;
         if (COUNT) cn.v[RT_CNT_B_BVH_TRI] += end - first;
         leaf_scan_min<COUNT>(sc.bvh_a, sc.bvh_bary, first, end, o, d, best, tk, cn);
-        cur = pop();
+        cur = bvh_pop(stk, sp, best);
         if (cur == RT_BVH_EMPTY) break;
     }
     pk.best = best;
@@ -368,14 +362,22 @@ __device__ __forceinline__ bool kd_certified(const RtDevScene &sc, const Vec3D o
 }
 
 // step 3: the reference's KD traversal with the skip bound s_min (-inf: the
-// plain traversal), from the scene box's [entry, root_exit]
-template <bool COUNT, typename STACK>
+// plain traversal, trace()) and T* (-1: none), from the scene box's [entry,
+// root_exit].  Returns the triangle or -1, the hit's barycentrics and hs = the
+// *t of the winning intersect_triangle (rt/trace_ray.cuh:90-97), the value
+// trace_leaf_node's smallest_t ends on — only with WANT_S: the occlusion
+// query's (trace_s, occluded_bvh); the render kernels leave hs alone.
+// The leaf visit — T*'s entry alone, else leaf_scan — stays written out here and
+// in wide_bvh.h kd_bounded_wave (they differ in the search for T*'s listing):
+// as one function taking the search, the search loop's exit compiles otherwise
+// and the render and query kernels change length (profiles/kd_step/README.md).
+template <bool COUNT, bool WANT_S = false, typename STACK>
 __device__ __forceinline__ int kd_bounded(const RtDevScene &sc, const Vec3D o, const Vec3D d, float entry,
                                           const float root_exit, const float s_min, const int tstar, float &hbx,
-                                          float &hby, float &hbz, STACK &stk, Cnt &c)
+                                          float &hby, float &hbz, float &hs, STACK &stk, Cnt &c)
 {
     float exit_ = root_exit;
-    const float yx = rt_recip_guard(d.x), yy = rt_recip_guard(d.y), yz = rt_recip_guard(d.z);
+    const Vec3D y = rt_v3(rt_recip_guard(d.x), rt_recip_guard(d.y), rt_recip_guard(d.z));
     int sp = 0;
     uint32_t node = 0;
     while (true) {
@@ -383,29 +385,8 @@ __device__ __forceinline__ int kd_bounded(const RtDevScene &sc, const Vec3D o, c
         if (COUNT) c.v[RT_CNT_NODE]++;
         while ((nd.y & 3u) != RT_LEAF_TAG) {
             const uint32_t axis = nd.y & 3u;
-            const float split = as_float(nd.x);
-            const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
-            const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
-            const float yax = axis == 0 ? yx : (axis == 1 ? yy : yz);
-            uint32_t near_c = node + 1, far_c = nd.y >> 2;
-            if (oax >= split) { // ray_behind_plane (:174-188)
-                near_c = nd.y >> 2;
-                far_c = node + 1;
-            }
-            const float t = rt_div_by(split - oax, dax, yax); // intersect_plane (:190-210)
-            if (t >= exit_ || t < 0) {
-                node = near_c;
-            } else if (t <= entry) {
-                node = far_c;
-            } else if (t <= s_min) { // the near side holds no hit: its leaves' exits are <= t
-                node = far_c;
-                entry = t;
-            } else {
-                stk.put(sp, far_c, t);
-                ++sp;
-                node = near_c;
-                exit_ = t;
-            }
+            kd_split_step<KD_DEVICE_DIV, KD_BOUNDED>(nd, kd_axis(axis, o), kd_axis(axis, d), kd_axis(axis, y), s_min, node,
+                                                     entry, exit_, sp, stk);
             nd = ldc_u2(sc.nodes + 2 * (size_t)node);
             if (COUNT) c.v[RT_CNT_NODE]++;
         }
@@ -449,22 +430,20 @@ __device__ __forceinline__ int kd_bounded(const RtDevScene &sc, const Vec3D o, c
                 be = leaf_scan<COUNT>(sc.isect_a, sc.isect_bary, e0, e1, o, d, smallest, bx, by, bz, c);
             }
             const int best = be >= 0 ? (int)ldc_u2(&sc.isect_bary[be].rd).y : -1;
-            if (best >= 0) {
+            // (a listed entry's triangle index is >= 0: WANT_S asks the entry, as the occlusion kernel always did)
+            if (WANT_S ? be >= 0 : best >= 0) {
                 if (COUNT) c.v[RT_CNT_HIT]++;
                 hbx = bx;
                 hby = by;
                 hbz = bz;
+                if (WANT_S) hs = smallest;
                 return best;
             }
         }
         if (sp == 0) return -1;
-        --sp;
-        node = stk.node_at(sp);
-        entry = stk.entry_at(sp);
-        exit_ = sp > 0 ? stk.entry_at(sp - 1) : root_exit;
+        kd_pop(stk, sp, root_exit, node, entry, exit_);
     }
 }
-
 
 // trace_ray with the bound: returns the triangle index or -1 and the hit's
 // barycentric coordinates, bit-identical to trace().  COUNT (RT_TRAVERSAL_
@@ -489,7 +468,8 @@ __device__ __forceinline__ int trace_bvh(const RtDevScene &sc, const Vec3D o, co
         int hit;
         if (kd_certified<COUNT>(sc, o, d, entry, root_exit, s_min, tk, hit, hbx, hby, hbz, c)) return hit;
     }
-    const int h = kd_bounded<COUNT>(sc, o, d, entry, root_exit, s_min, tstar, hbx, hby, hbz, stk, c);
+    float hs; // (the occlusion query's)
+    const int h = kd_bounded<COUNT>(sc, o, d, entry, root_exit, s_min, tstar, hbx, hby, hbz, hs, stk, c);
     if (COUNT && h >= 0) c.cert[1]++;
     return h;
 }
@@ -525,98 +505,13 @@ __device__ __forceinline__ int trace_bvh_park(const RtDevScene &sc, const Vec3D 
         s_min = pk.best;
         if (pk.tk >= 0) tstar = (int)sc.bvh_bary[pk.tk].tri;
     }
-    hit = kd_bounded<COUNT>(sc, o, d, entry, root_exit, s_min, tstar, hbx, hby, hbz, stk, c);
+    float hs; // (the occlusion query's)
+    hit = kd_bounded<COUNT>(sc, o, d, entry, root_exit, s_min, tstar, hbx, hby, hbz, hs, stk, c);
     if (COUNT && hit >= 0) c.cert[1]++;
     return RT_PARK_DONE;
 }
 
 // ---- the occlusion query (rt_occluded, query.hip) ----
-// kd_bounded restated so that it yields the winning ray parameter instead of
-// the barycentrics: hs = the *t of the winning intersect_triangle
-// (rt/trace_ray.cuh:90-97), the value trace_leaf_node's smallest_t ends on
-// (`st` in the T* leaf, `smallest` after leaf_scan).  The descent, the T*
-// leaf and the leaf scan are kd_bounded's, statement for statement; with
-// s_min = -inf and tstar = -1 it is the plain traversal, trace().  A function
-// of its own: the render kernels' kd_bounded stays as it is.
-template <typename STACK>
-__device__ __forceinline__ int kd_bounded_s(const RtDevScene &sc, const Vec3D o, const Vec3D d, float entry,
-                                            const float root_exit, const float s_min, const int tstar, float &hs,
-                                            STACK &stk, Cnt &c)
-{
-    float exit_ = root_exit;
-    const float yx = rt_recip_guard(d.x), yy = rt_recip_guard(d.y), yz = rt_recip_guard(d.z);
-    int sp = 0;
-    uint32_t node = 0;
-    while (true) {
-        uint2 nd = ldc_u2(sc.nodes + 2 * (size_t)node);
-        while ((nd.y & 3u) != RT_LEAF_TAG) {
-            const uint32_t axis = nd.y & 3u;
-            const float split = as_float(nd.x);
-            const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
-            const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
-            const float yax = axis == 0 ? yx : (axis == 1 ? yy : yz);
-            uint32_t near_c = node + 1, far_c = nd.y >> 2;
-            if (oax >= split) { // ray_behind_plane (:174-188)
-                near_c = nd.y >> 2;
-                far_c = node + 1;
-            }
-            const float t = rt_div_by(split - oax, dax, yax); // intersect_plane (:190-210)
-            if (t >= exit_ || t < 0) {
-                node = near_c;
-            } else if (t <= entry) {
-                node = far_c;
-            } else if (t <= s_min) { // the near side holds no hit: its leaves' exits are <= t
-                node = far_c;
-                entry = t;
-            } else {
-                stk.put(sp, far_c, t);
-                ++sp;
-                node = near_c;
-                exit_ = t;
-            }
-            nd = ldc_u2(sc.nodes + 2 * (size_t)node);
-        }
-        const uint32_t count = nd.y >> 2;
-        if (count > 0 && exit_ > s_min) {
-            // trace_leaf_node (:115-172): closest starts at the leaf's exit
-            float smallest = exit_;
-            float bx = 0.0f, by = 0.0f, bz = 0.0f;
-            int be = -1;
-            const uint32_t e0 = nd.x, e1 = nd.x + count;
-            if (tstar >= 0) { // the T* leaf (kd_bounded)
-                uint32_t at = e1;
-                for (uint32_t e = e0; e < e1 && at == e1; e += 4) {
-                    uint32_t id[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) id[k] = *(const RT_CONST uint32_t *)(sc.isect_tri + (e + k < e1 ? e + k : e));
-#pragma unroll
-                    for (int k = 3; k >= 0; --k)
-                        if (e + k < e1 && id[k] == (uint32_t)tstar) at = e + k;
-                }
-                if (at != e1) {
-                    float st;
-                    if (rt_tri_plane(ldc4(sc.isect_a + at), o, d, smallest, st) &&
-                        rt_tri_bary(ldc4(&sc.isect_bary[at].b), ldc4(&sc.isect_bary[at].c), ldc4(&sc.isect_bary[at].d),
-                                    ldc_f(&sc.isect_bary[at].rd), o, d, st, bx, by, bz)) {
-                        smallest = st;
-                        be = (int)at;
-                    }
-                }
-            }
-            if (be < 0) be = leaf_scan<false>(sc.isect_a, sc.isect_bary, e0, e1, o, d, smallest, bx, by, bz, c);
-            if (be >= 0) { // (the triangle index of a listed entry is >= 0)
-                hs = smallest;
-                return (int)ldc_u2(&sc.isect_bary[be].rd).y;
-            }
-        }
-        if (sp == 0) return -1;
-        --sp;
-        node = stk.node_at(sp);
-        entry = stk.entry_at(sp);
-        exit_ = sp > 0 ? stk.entry_at(sp - 1) : root_exit;
-    }
-}
-
 // trace_ray's hit and its ray parameter by the plain KD traversal (the rays
 // outside the bound's domain, RT_TRAVERSAL_KD): -1 = miss
 template <typename STACK>
@@ -625,7 +520,8 @@ __device__ __forceinline__ int trace_s(const RtDevScene &sc, const Vec3D o, cons
 {
     float entry, exit_;
     if (!bbox_hit(sc, o, d, entry, exit_)) return -1;
-    return kd_bounded_s(sc, o, d, entry, exit_, -INFINITY, -1, hs, stk, c);
+    float bx, by, bz;
+    return kd_bounded<false, true>(sc, o, d, entry, exit_, -INFINITY, -1, bx, by, bz, hs, stk, c);
 }
 
 // Whether trace_ray hits with a ray parameter s < tmax (tmax > 1e-5: the
@@ -657,8 +553,8 @@ __device__ __forceinline__ bool occluded_bvh(const RtDevScene &sc, const Vec3D o
         early = true;
         return false;
     }
-    float s = INFINITY;
-    const int tri = kd_bounded_s(sc, o, d, entry, root_exit, s_min, tstar, s, stk, c);
+    float s = INFINITY, bx, by, bz;
+    const int tri = kd_bounded<false, true>(sc, o, d, entry, root_exit, s_min, tstar, bx, by, bz, s, stk, c);
     return tri >= 0 && s < tmax;
 }
 

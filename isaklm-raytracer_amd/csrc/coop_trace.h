@@ -35,16 +35,8 @@ __device__ __forceinline__ bool coop_bary(const RtDevScene &sc, uint32_t k, Vec3
     const RtIsectBary *rec = sc.isect_bary + k;
     const RtF4 B = ldf4(&rec->b), C = ldf4(&rec->c), D = ldf4(&rec->d);
     const uint2 R = *reinterpret_cast<const uint2 *>(&rec->rd);
-    const float rd = __uint_as_float(R.x);
-    const float px = o.x + d.x * s, py = o.y + d.y * s, pz = o.z + d.z * s;
-    const float v2x = px - B.x, v2y = py - B.y, v2z = pz - B.z;
-    const float d20 = v2x * C.x + v2y * C.y + v2z * C.z;
-    const float d21 = v2x * D.x + v2y * D.y + v2z * D.z;
-    cy = (D.w * d20 - C.w * d21) * rd;
-    cz = (B.w * d21 - C.w * d20) * rd;
-    cx = 1.0f - cy - cz;
     tri = (int)R.y;
-    return rt_bary_inside(cx, cy, cz);
+    return rt_tri_bary(B, C, D, __uint_as_float(R.x), o, d, s, cx, cy, cz);
 }
 
 // A plane-test candidate in the per-wave LDS list: (entry << 6 | owner lane),
@@ -126,15 +118,6 @@ __device__ __forceinline__ bool coop_begin(const RtDevScene &sc, CoopRay &r, Vec
     return r.live;
 }
 
-// pop the next subtree (rt/trace_ray.cuh:308-316); exit t = entry of the entry below
-template <typename STK>
-__device__ __forceinline__ void coop_pop(CoopRay &r, STK &stk)
-{
-    --r.sp;
-    stk.get(r.sp, r.node, r.entry);
-    r.exit_ = r.sp > 0 ? stk.entry_at(r.sp - 1) : r.root_exit;
-}
-
 // Descent (rt/trace_ray.cuh:273-306) of a live, non-pending lane for at most
 // `cap` node fetches, stopping at the first non-empty leaf (r.pend).  Empty
 // leaves are popped on the spot.  Returns true when the ray ended (a miss:
@@ -198,32 +181,15 @@ __device__ __forceinline__ bool coop_descend(const RtDevScene &sc, CoopRay &r, S
                 act = false;
             } else {
                 if (COUNT && r.sp - 1 >= WF_LDS_STACK) c.v[RT_CNT_SPILL_POP]++;
-                coop_pop(r, stk);
+                kd_pop(stk, r.sp, r.root_exit, r.node, r.entry, r.exit_);
             }
             continue;
         }
         const uint32_t axis = nd.y & 3u;
-        const float split = as_float(nd.x);
-        const float oax = axis == 0 ? ox : (axis == 1 ? oy : oz);
-        const float dax = axis == 0 ? dx : (axis == 1 ? dy : dz);
-        const float yax = axis == 0 ? yx : (axis == 1 ? yy : yz);
-        uint32_t near_c = r.node + 1, far_c = nd.y >> 2;
-        if (oax >= split) { // ray_behind_plane (:174-188)
-            near_c = nd.y >> 2;
-            far_c = r.node + 1;
-        }
-        const float t = rt_div_by(split - oax, dax, yax); // intersect_plane (:190-210): (split - o) / d
-        if (t >= r.exit_ || t < 0) {
-            r.node = near_c;
-        } else if (t <= r.entry) {
-            r.node = far_c;
-        } else {
-            if (COUNT && r.sp >= RT_REF_STACK) c.v[RT_CNT_DEEP_PUSH]++;
-            if (COUNT && r.sp >= WF_LDS_STACK) c.v[RT_CNT_SPILL_PUSH]++;
-            stk.put(r.sp, far_c, t);
-            ++r.sp;
-            r.node = near_c;
-            r.exit_ = t;
+        if (kd_split_step<KD_DEVICE_DIV, KD_PLAIN>(nd, kd_axis(axis, ox, oy, oz), kd_axis(axis, dx, dy, dz),
+                                                   kd_axis(axis, yx, yy, yz), 0.0f, r.node, r.entry, r.exit_, r.sp, stk)) {
+            if (COUNT && r.sp - 1 >= RT_REF_STACK) c.v[RT_CNT_DEEP_PUSH]++;
+            if (COUNT && r.sp - 1 >= WF_LDS_STACK) c.v[RT_CNT_SPILL_PUSH]++;
         }
 #if WF_NODE_PAIRS
         if (loaded && r.node == at + 1) {
@@ -393,7 +359,7 @@ __device__ __forceinline__ bool coop_leaves(const RtDevScene &sc, CoopRay &r, ST
             done = true;
         } else {
             if (COUNT && r.sp - 1 >= WF_LDS_STACK) c.v[RT_CNT_SPILL_POP]++;
-            coop_pop(r, stk);
+            kd_pop(stk, r.sp, r.root_exit, r.node, r.entry, r.exit_);
         }
     }
     return done;
@@ -560,16 +526,9 @@ __device__ __forceinline__ void wide_trace_from(const RtDevScene &sc, Vec3D o, V
                     const float dn = dx * A.x + dy * A.y + dz * A.z;
                     const float s = (A.w - (ox * A.x + oy * A.y + oz * A.z)) / dn; // intersect_triangle (:95-98)
                     if (dn != 0 && s >= 0.00001f && s < ex) {
-                        const float px = ox + dx * s, py = oy + dy * s, pz = oz + dz * s; // = coop_bary
-                        const float v2x = px - B.x, v2y = py - B.y, v2z = pz - B.z;
-                        const float d20 = v2x * C.x + v2y * C.y + v2z * C.z;
-                        const float d21 = v2x * D.x + v2y * D.y + v2z * D.z;
-                        const float rd = __uint_as_float(R.x);
-                        cy = (D.w * d20 - C.w * d21) * rd;
-                        cz = (B.w * d21 - C.w * d20) * rd;
-                        cx = 1.0f - cy - cz;
                         t = (int)R.y;
-                        if (rt_bary_inside(cx, cy, cz)) {
+                        if (rt_tri_bary(B, C, D, __uint_as_float(R.x), rt_v3(ox, oy, oz), rt_v3(dx, dy, dz), s, cx, cy,
+                                        cz)) { // (= coop_bary)
                             mine = ((unsigned long long)j << 58) | ((unsigned long long)__float_as_uint(s) << 26) |
                                    (unsigned long long)e;
                             atomicMin(wkey, mine);

@@ -3,7 +3,7 @@
 // the CPU over the arrays prepare_host produces, for the programs that compare
 // it ray by ray with the plain KD traversal (trace_ray):
 //
-//   kd_descent   bvh_trace.h kd_bounded / kd_bounded_s, statement for statement
+//   kd_descent   bvh_trace.h kd_bounded over rt_kernels.h kd_split_step / kd_pop, statement for statement
 //   bvh4_smin    bvh_trace.h bvh4_query + bvh4_children + leaf_scan_min
 //   bvh_bound    bvh_trace.h bvh_bound (the binary tree; the 4-wide query's cross-check)
 //   kd_resume    coop_trace.h kd_origin_frontier's replay, cell_of its grid lookup
@@ -108,7 +108,8 @@ struct Resume {
 enum Division { IEEE_DIV, DEVICE_DIV };       // t = (split - o) / d by `/`, or by rt_recip_guard + rt_div_by
 enum TstarMiss { WHOLE_LEAF, HARD_FAILURE };  // a T* entry that does not pass: the device's fall-back, or exit(3)
 
-// bvh_trace.h kd_bounded / kd_bounded_s: the reference's KD traversal with the
+// bvh_trace.h kd_bounded (its split step and pop: rt_kernels.h kd_split_step,
+// kd_pop — Division is their KdDivision): the reference's KD traversal with the
 // skip bound s_min (-inf: the plain traversal, trace_ray itself) from the scene
 // box's [entry, root_exit]; tstar >= 0: a leaf that lists T* tests T*'s first
 // entry alone.  `from`: the start state of the origin-cell replay (kd_resume).

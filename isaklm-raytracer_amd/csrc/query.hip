@@ -182,17 +182,6 @@ __device__ __forceinline__ int query_trace(const RtDevScene &sc, int kd_only, Ve
     return trace_bvh<false>(sc, o, d, bx, by, bz, stk, c);
 }
 
-// the next ray index for each lane that is here (the counter stops below n + the grid's threads: no wrap)
-__device__ __forceinline__ uint32_t wave_next_index(uint32_t *fetch, int lane)
-{
-    const unsigned long long m = __ballot(true);
-    const int leader = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 // stats[k] += the wave's sum of lane_counts[k], by lane 0 and only where the sum is not zero (every lane
 // of the wave calls this: the kernels' loop exits reconverge before it)
 template <int N>

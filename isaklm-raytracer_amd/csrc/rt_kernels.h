@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "bvh_common.h"
 #include "rt_device.h"
 #include "rt_vecmath.h"
 #include "sampler_math.h"
@@ -205,6 +206,127 @@ struct Stack {
     }
 };
 
+// ---- the KD traversal's shared steps (DESIGN.md §5 "The shared traversal steps") ----
+// Every KD traversal of the library makes its inner-node decision and its pop
+// with the functions below, so the exactness arguments rest on one arithmetic
+// (trace, bvh_trace.h kd_bounded, wide_bvh.h kd_bounded_wave, coop_trace.h
+// coop_descend, wf_queue_kernels.h wf_trace_bvh_dyn / wf_trace_dyn).  The
+// compile-time choices are those of the host model (host/trace_host.h
+// kd_descent): the division, and whether the s_min arm exists.
+enum KdDivision { KD_IEEE_DIV, KD_DEVICE_DIV }; // t = (split - o) / d by `/`, or by rt_div_by on rt_recip_guard(d)
+enum KdBound { KD_PLAIN, KD_BOUNDED };          // the reference's chain, or with the skip bound s_min (bvh_trace.h)
+
+__device__ __forceinline__ float kd_axis(uint32_t axis, float x, float y, float z)
+{
+    return axis == 0 ? x : (axis == 1 ? y : z);
+}
+__device__ __forceinline__ float kd_axis(uint32_t axis, Vec3D v) { return kd_axis(axis, v.x, v.y, v.z); }
+
+// One inner-node decision of trace_ray (rt/trace_ray.cuh:273-306) at `node`,
+// whose words are nd (loaded by the caller: plain, constant-space, LDS block or
+// node-pair loads), for the ray's origin / direction / guarded reciprocal on
+// the node's axis (yax: unused with KD_IEEE_DIV; s_min: unused with KD_PLAIN).
+// Returns whether the far child was pushed (at index sp - 1): the event the
+// counting callers count (RT_CNT_DEEP_PUSH, RT_CNT_SPILL_PUSH).
+template <KdDivision DIV, KdBound BOUND, typename STACK>
+__device__ __forceinline__ bool kd_split_step(const uint2 nd, const float oax, const float dax, const float yax,
+                                              const float s_min, uint32_t &node, float &entry, float &exit_, int &sp,
+                                              STACK &stk)
+{
+    const float split = as_float(nd.x);
+    uint32_t near_c = node + 1, far_c = nd.y >> 2;
+    if (oax >= split) { // ray_behind_plane (:174-188)
+        near_c = nd.y >> 2;
+        far_c = node + 1;
+    }
+    const float t = DIV == KD_DEVICE_DIV ? rt_div_by(split - oax, dax, yax) : (split - oax) / dax; // intersect_plane (:190-210)
+    if (t >= exit_ || t < 0) {
+        node = near_c;
+    } else if (t <= entry) {
+        node = far_c;
+    } else if (BOUND == KD_BOUNDED && t <= s_min) { // the near side holds no hit: its leaves' exits are <= t
+        node = far_c;
+        entry = t;
+    } else {
+        stk.put(sp, far_c, t);
+        ++sp;
+        node = near_c;
+        exit_ = t;
+        return true;
+    }
+    return false;
+}
+
+// pop the next subtree (rt/trace_ray.cuh:308-316; sp > 0); its exit t = the entry of the entry below, or the root's exit
+template <typename STACK>
+__device__ __forceinline__ void kd_pop(STACK &stk, int &sp, const float root_exit, uint32_t &node, float &entry,
+                                       float &exit_)
+{
+    const int k = sp - 1;
+    node = stk.node_at(k);
+    entry = stk.entry_at(k);
+    exit_ = k > 0 ? stk.entry_at(k - 1) : root_exit;
+    sp = k;
+}
+
+// trace_leaf_node (:115-172) + intersect_triangle (:73-113) over leaf entries
+// [e0, e1), two entries per step so both plane loads (and both barycentric
+// record loads) are in flight together.  A hit needs dn != 0, s >= 1e-5,
+// s < closest and barycentrics in [0,1]; the plane part is pre-screened against
+// the closest t at the start of the step (a superset) and re-checked in entry
+// order, so the winner is the reference's.  `smallest`: the leaf's exit.
+// Returns the winner's triangle (-1: none; bx, by, bz are then left alone).
+// wf_trace_dyn's leaf; trace() below carries the same loop written out.
+template <bool COUNT>
+__device__ __forceinline__ int leaf_scan_pairs(const RtDevScene &sc, const uint32_t e0, const uint32_t e1, const Vec3D o,
+                                               const Vec3D d, float smallest, float &bx, float &by, float &bz, Cnt &c)
+{
+    int best = -1;
+    for (uint32_t e = e0; e < e1; e += 2) {
+        const bool two = e + 1 < e1;
+        if (COUNT) c.v[RT_CNT_TRI] += two ? 2 : 1;
+        const RtF4 A0 = ldf4(sc.isect_a + e); // n, d
+        const RtF4 A1 = ldf4(sc.isect_a + (two ? e + 1 : e));
+        const float dn0 = d.x * A0.x + d.y * A0.y + d.z * A0.z;
+        const float dn1 = d.x * A1.x + d.y * A1.y + d.z * A1.z;
+        const float s0 = (A0.w - (o.x * A0.x + o.y * A0.y + o.z * A0.z)) / dn0;
+        const float s1 = (A1.w - (o.x * A1.x + o.y * A1.y + o.z * A1.z)) / dn1;
+        const bool p0 = dn0 != 0 && s0 >= 0.00001f && s0 < smallest;
+        const bool p1 = two && dn1 != 0 && s1 >= 0.00001f && s1 < smallest;
+        RtF4 B0, C0, D0, B1, C1, D1;
+        uint2 R0, R1;
+        if (p0) {
+            B0 = ldf4(&sc.isect_bary[e].b); // p1, d00
+            C0 = ldf4(&sc.isect_bary[e].c); // v0, d01
+            D0 = ldf4(&sc.isect_bary[e].d); // v1, d11
+            R0 = *reinterpret_cast<const uint2 *>(&sc.isect_bary[e].rd);
+        }
+        if (p1) {
+            B1 = ldf4(&sc.isect_bary[e + 1].b);
+            C1 = ldf4(&sc.isect_bary[e + 1].c);
+            D1 = ldf4(&sc.isect_bary[e + 1].d);
+            R1 = *reinterpret_cast<const uint2 *>(&sc.isect_bary[e + 1].rd);
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const bool p = k == 0 ? p0 : p1;
+            const float s = k == 0 ? s0 : s1;
+            if (!p || !(s < smallest)) continue;
+            const RtF4 B = k == 0 ? B0 : B1, C = k == 0 ? C0 : C1, D = k == 0 ? D0 : D1;
+            const uint2 R = k == 0 ? R0 : R1;
+            float cx, cy, cz;
+            if (rt_tri_bary(B, C, D, as_float(R.x), o, d, s, cx, cy, cz)) {
+                smallest = s;
+                best = (int)R.y;
+                bx = cx;
+                by = cy;
+                bz = cz;
+            }
+        }
+    }
+    return best;
+}
+
 // trace_ray (rt/trace_ray.cuh:244-318): closest hit inside the first leaf
 // (front to back) that has one.  Returns the triangle index or -1 and the
 // barycentric coordinates of the hit.
@@ -213,47 +335,28 @@ __device__ __forceinline__ int trace(const RtDevScene &sc, const Vec3D o, const 
                                      float &hbz, STACK &stk, Cnt &c)
 {
     if (COUNT) c.v[RT_CNT_RAY]++;
-    float entry, exit_;
-    if (!bbox_hit(sc, o, d, entry, exit_)) return -1;
-    const float root_exit = exit_;
+    // (declared in this order: the compiler orders the loop-carried copies of the four by it, and this
+    // one gives the kernels the instruction stream they had — profiles/kd_step/README.md)
     int sp = 0;
     uint32_t node = 0;
+    float exit_, entry;
+    if (!bbox_hit(sc, o, d, entry, exit_)) return -1;
+    const float root_exit = exit_;
     while (true) {
         uint2 nd = *reinterpret_cast<const uint2 *>(sc.nodes + 2 * (size_t)node);
         if (COUNT) c.v[RT_CNT_NODE]++;
         while ((nd.y & 3u) != RT_LEAF_TAG) {
             const uint32_t axis = nd.y & 3u;
-            const float split = as_float(nd.x);
-            const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
-            const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
-            uint32_t near_c = node + 1, far_c = nd.y >> 2;
-            if (oax >= split) { // ray_behind_plane (:174-188)
-                near_c = nd.y >> 2;
-                far_c = node + 1;
-            }
-            const float t = (split - oax) / dax; // intersect_plane (:190-210)
-            if (t >= exit_ || t < 0) {
-                node = near_c;
-            } else if (t <= entry) {
-                node = far_c;
-            } else {
-                if (COUNT && sp >= RT_REF_STACK) c.v[RT_CNT_DEEP_PUSH]++;
-                stk.put(sp, far_c, t);
-                ++sp;
-                node = near_c;
-                exit_ = t;
-            }
+            const bool pushed = kd_split_step<KD_IEEE_DIV, KD_PLAIN>(nd, kd_axis(axis, o), kd_axis(axis, d), 0.0f, 0.0f,
+                                                                     node, entry, exit_, sp, stk);
+            if (COUNT && pushed && sp - 1 >= RT_REF_STACK) c.v[RT_CNT_DEEP_PUSH]++;
             nd = *reinterpret_cast<const uint2 *>(sc.nodes + 2 * (size_t)node);
             if (COUNT) c.v[RT_CNT_NODE]++;
         }
         const int count = (int)(nd.y >> 2);
         if (count > 0) {
-            // trace_leaf_node (:115-172) + intersect_triangle (:73-113), two
-            // entries per step so both plane loads (and both Cramer loads) are
-            // in flight together.  A hit needs dn != 0, s >= 1e-5, s < closest
-            // and barycentrics in [0,1]; the plane part is pre-screened against
-            // the closest t at the start of the step (a superset) and
-            // re-checked in entry order, so the winner is the reference's.
+            // leaf_scan_pairs' loop, written out: as a call it costs rt_path_kernel<false, 20, false> 18 scratch
+            // accesses (spilled registers) where this text has none (profiles/kd_step/README.md)
             const uint32_t e0 = nd.x, e1 = nd.x + (uint32_t)count;
             float smallest = exit_;
             int best = -1;
@@ -290,15 +393,8 @@ __device__ __forceinline__ int trace(const RtDevScene &sc, const Vec3D o, const 
                     if (!p || !(s < smallest)) continue;
                     const RtF4 B = k == 0 ? B0 : B1, C = k == 0 ? C0 : C1, D = k == 0 ? D0 : D1;
                     const uint2 R = k == 0 ? R0 : R1;
-                    const float rd = as_float(R.x);
-                    const float px = o.x + d.x * s, py = o.y + d.y * s, pz = o.z + d.z * s;
-                    const float v2x = px - B.x, v2y = py - B.y, v2z = pz - B.z;
-                    const float d20 = v2x * C.x + v2y * C.y + v2z * C.z;
-                    const float d21 = v2x * D.x + v2y * D.y + v2z * D.z;
-                    const float cy = (D.w * d20 - C.w * d21) * rd;
-                    const float cz = (B.w * d21 - C.w * d20) * rd;
-                    const float cx = 1.0f - cy - cz;
-                    if (rt_bary_inside(cx, cy, cz)) {
+                    float cx, cy, cz;
+                    if (rt_tri_bary(B, C, D, as_float(R.x), o, d, s, cx, cy, cz)) {
                         smallest = s;
                         best = (int)R.y;
                         bx = cx;
@@ -316,10 +412,7 @@ __device__ __forceinline__ int trace(const RtDevScene &sc, const Vec3D o, const 
             }
         }
         if (sp == 0) return -1;
-        --sp;
-        node = stk.node_at(sp);
-        entry = stk.entry_at(sp);
-        exit_ = sp > 0 ? stk.entry_at(sp - 1) : root_exit;
+        kd_pop(stk, sp, root_exit, node, entry, exit_);
     }
 }
 
@@ -641,6 +734,17 @@ __device__ __forceinline__ float4 miss_record() // hits[]: tri = -1, no barycent
 {
     return make_float4(__int_as_float(vconst(-1)), __int_as_float(vconst(0)), __int_as_float(vconst(0)),
                        __int_as_float(vconst(0)));
+}
+// the next queue index for each lane that is here (one wave-aggregated atomic; the counter stops below n + the
+// grid's threads: no wrap).  Call from the lanes that want an index: they are the ballot.
+__device__ __forceinline__ uint32_t wave_next_index(uint32_t *fetch, int lane)
+{
+    const unsigned long long m = __ballot(true);
+    const int leader = __ffsll((long long)m) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
+    base = __shfl(base, leader);
+    return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
 }
 __device__ __forceinline__ int lane63(int v) { return __builtin_amdgcn_readlane(v, 63); }
 

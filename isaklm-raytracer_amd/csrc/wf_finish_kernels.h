@@ -613,25 +613,17 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_FIN_OCC) wf_finish_coop(RtDevScen
     bool pending = false;             // a finished ray query waiting for shade_step
     while (true) {
         // ---- idle lanes take the next queued paths
-        const bool need = !active && !exhausted;
-        const unsigned long long m = __ballot(need);
-        if (m) {
-            const int leader = __ffsll((long long)m) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
-            base = __shfl(base, leader);
-            if (need) {
-                const uint32_t e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                if (e >= n) {
-                    exhausted = true;
-                } else {
-                    active = true;
-                    first_ray(st, fr, st.q_slot[q][e], p);
-                    if (COUNT) c.v[RT_CNT_RAY]++;
-                    if (!coop_begin(sc, r, p.ro, p.rd)) {
-                        pending = true;
-                        hit = -1;
-                    }
+        if (!active && !exhausted) {
+            const uint32_t e = wave_next_index(fetch, lane);
+            if (e >= n) {
+                exhausted = true;
+            } else {
+                active = true;
+                first_ray(st, fr, st.q_slot[q][e], p);
+                if (COUNT) c.v[RT_CNT_RAY]++;
+                if (!coop_begin(sc, r, p.ro, p.rd)) {
+                    pending = true;
+                    hit = -1;
                 }
             }
         }

@@ -26,6 +26,16 @@ __device__ __forceinline__ bool start_sample(const RtDevFrame &fr, const RtDevCa
     return false;
 }
 
+// ray e's 16-byte record in hits[]: the triangle and the hit's barycentrics, or a miss (miss_record)
+__device__ __forceinline__ void store_hit(const WfState &st, uint32_t e, int tri, float bx, float by, float bz)
+{
+    *reinterpret_cast<float4 *>(st.hits + e) = make_float4(__int_as_float(tri), bx, by, bz);
+}
+__device__ __forceinline__ void store_miss(const WfState &st, uint32_t e)
+{
+    *reinterpret_cast<float4 *>(st.hits + e) = miss_record();
+}
+
 } // namespace
 
 template <bool COUNT>
@@ -93,7 +103,7 @@ __global__ void __launch_bounds__(WF_BLOCK) wf_trace(RtDevScene sc, WfState st, 
             const RtF4 o4 = ldf4(rays + 2 * (size_t)e), d4 = ldf4(rays + 2 * (size_t)e + 1);
             float bx = 0.0f, by = 0.0f, bz = 0.0f;
             const int hit = trace<COUNT>(sc, ld3(o4), ld3(d4), bx, by, bz, stk, c);
-            *reinterpret_cast<float4 *>(st.hits + e) = make_float4(__int_as_float(hit), bx, by, bz);
+            store_hit(st, e, hit, bx, by, bz);
         }
     }
     if (COUNT) flush_counters(c, counters);
@@ -141,37 +151,29 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_DYN_WAVES) wf_trace_bvh_dyn(RtDev
     float best = 0.0f, entry = 0.0f, exit_ = 0.0f, root_exit = 0.0f, s_min = 0.0f;
     while (true) {
         // ---- refill: lanes without a ray take the next queued one
-        const bool need = phase == 0 && !exhausted;
-        const unsigned long long mm = __ballot(need);
-        if (mm) {
-            const int leader = __ffsll((long long)mm) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(mm));
-            base = __shfl(base, leader);
-            if (need) {
-                e = base + (uint32_t)__popcll(mm & ((1ull << lane) - 1ull));
-                if (e >= n) {
-                    exhausted = true;
+        if (phase == 0 && !exhausted) {
+            e = wave_next_index(fetch, lane);
+            if (e >= n) {
+                exhausted = true;
+            } else {
+                o = ld3(ldf4(rays + 2 * (size_t)e));
+                d = ld3(ldf4(rays + 2 * (size_t)e + 1));
+                if (COUNT) c.v[RT_CNT_RAY]++;
+                if (!bbox_hit(sc, o, d, entry, exit_)) {
+                    store_miss(st, e);
                 } else {
-                    o = ld3(ldf4(rays + 2 * (size_t)e));
-                    d = ld3(ldf4(rays + 2 * (size_t)e + 1));
-                    if (COUNT) c.v[RT_CNT_RAY]++;
-                    if (!bbox_hit(sc, o, d, entry, exit_)) {
-                        *reinterpret_cast<float4 *>(st.hits + e) = miss_record();
+                    root_exit = exit_;
+                    sp = 0;
+                    if (rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
+                        phase = 1;
+                        sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, sc.bvh_scale));
+                        best = exit_;
+                        cur = 0;
                     } else {
-                        root_exit = exit_;
-                        sp = 0;
-                        if (rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
-                            phase = 1;
-                            sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, sc.bvh_scale));
-                            best = exit_;
-                            cur = 0;
-                        } else {
-                            phase = 2; // the plain KD traversal
-                            s_min = -INFINITY;
-                            node = 0;
-                            nd_ok = false;
-                        }
+                        phase = 2; // the plain KD traversal
+                        s_min = -INFINITY;
+                        node = 0;
+                        nd_ok = false;
                     }
                 }
             }
@@ -187,20 +189,7 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_DYN_WAVES) wf_trace_bvh_dyn(RtDev
             if (step) {
                 if (COUNT) c.v[RT_CNT_B_BVH_NODE]++;
                 const uint32_t next = bvh4_children(sc, cur, sl, best, stk, sp);
-                if (next != RT_BVH_EMPTY) {
-                    cur = next;
-                } else { // pop the next subtree that may still hold a smaller s
-                    cur = RT_BVH_EMPTY;
-                    while (sp > 0) {
-                        uint32_t nn;
-                        float tn;
-                        stk.get(--sp, nn, tn);
-                        if (tn <= best) {
-                            cur = nn;
-                            break;
-                        }
-                    }
-                }
+                cur = next != RT_BVH_EMPTY ? next : bvh_pop(stk, sp, best);
             }
         }
         // (cur == RT_BVH_EMPTY carries the leaf bit: such a lane is done with the query)
@@ -210,21 +199,12 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_DYN_WAVES) wf_trace_bvh_dyn(RtDev
             if (COUNT) c.v[RT_CNT_B_BVH_TRI] += end - first;
             float bx, by, bz;
             (void)leaf_scan<COUNT>(sc.bvh_a, sc.bvh_bary, first, end, o, d, best, bx, by, bz, c);
-            cur = RT_BVH_EMPTY;
-            while (sp > 0) {
-                uint32_t nn;
-                float tn;
-                stk.get(--sp, nn, tn);
-                if (tn <= best) {
-                    cur = nn;
-                    break;
-                }
-            }
+            cur = bvh_pop(stk, sp, best);
         }
         if (phase == 1 && cur == RT_BVH_EMPTY) { // the query is over: s_min, then the KD phase (or a miss)
             s_min = best;
             if (!(s_min < root_exit)) {
-                *reinterpret_cast<float4 *>(st.hits + e) = miss_record();
+                store_miss(st, e);
                 phase = 0;
             } else {
                 phase = 2;
@@ -240,29 +220,9 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_DYN_WAVES) wf_trace_bvh_dyn(RtDev
             if (!__any(step)) break;
             if (step) {
                 if (nd_ok) { // an inner node: the reference's split step
-                    const uint32_t axis = nd.y & 3u;
-                    const float split = as_float(nd.x);
-                    const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
-                    const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
-                    const float yax = rt_recip_guard(dax);
-                    uint32_t near_c = node + 1, far_c = nd.y >> 2;
-                    if (oax >= split) { // ray_behind_plane (rt/trace_ray.cuh:174-188)
-                        near_c = nd.y >> 2;
-                        far_c = node + 1;
-                    }
-                    const float t = rt_div_by(split - oax, dax, yax); // intersect_plane (:190-210)
-                    if (t >= exit_ || t < 0) {
-                        node = near_c;
-                    } else if (t <= entry) {
-                        node = far_c;
-                    } else if (t <= s_min) { // the near side holds no hit: its leaves' exits are <= t
-                        node = far_c;
-                        entry = t;
-                    } else {
-                        stk.put(sp++, far_c, t);
-                        node = near_c;
-                        exit_ = t;
-                    }
+                    const float dax = kd_axis(nd.y & 3u, d);
+                    kd_split_step<KD_DEVICE_DIV, KD_BOUNDED>(nd, kd_axis(nd.y & 3u, o), dax, rt_recip_guard(dax), s_min,
+                                                             node, entry, exit_, sp, stk);
                 }
                 nd = ldc_u2(sc.nodes + 2 * (size_t)node);
                 nd_ok = true;
@@ -283,16 +243,13 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_DYN_WAVES) wf_trace_bvh_dyn(RtDev
             }
             if (best_tri >= 0) {
                 if (COUNT) c.v[RT_CNT_HIT]++;
-                *reinterpret_cast<float4 *>(st.hits + e) = make_float4(__int_as_float(best_tri), bx, by, bz);
+                store_hit(st, e, best_tri, bx, by, bz);
                 phase = 0;
             } else if (sp == 0) {
-                *reinterpret_cast<float4 *>(st.hits + e) = miss_record();
+                store_miss(st, e);
                 phase = 0;
             } else {
-                --sp;
-                node = stk.node_at(sp);
-                entry = stk.entry_at(sp);
-                exit_ = sp > 0 ? stk.entry_at(sp - 1) : root_exit;
+                kd_pop(stk, sp, root_exit, node, entry, exit_);
                 nd_ok = false;
             }
         }
@@ -303,7 +260,8 @@ __global__ void __launch_bounds__(WF_BLOCK, WF_DYN_WAVES) wf_trace_bvh_dyn(RtDev
 // Persistent trace with dynamic ray fetch: every lane runs rays one leaf at a
 // time; a lane whose ray is done writes its hit and takes the next queued ray
 // at the next leaf boundary (one wave-aggregated atomic), so a wave is never
-// held by its slowest ray.  Same per-ray arithmetic as trace().
+// held by its slowest ray.  The per-ray arithmetic is trace()'s own: the same split step, leaf scan and pop
+// (rt_kernels.h kd_split_step, leaf_scan_pairs, kd_pop).
 template <bool COUNT>
 __global__ void __launch_bounds__(WF_BLOCK) wf_trace_dyn(RtDevScene sc, WfState st, int q,
                                                          unsigned long long *counters)
@@ -327,29 +285,21 @@ __global__ void __launch_bounds__(WF_BLOCK) wf_trace_dyn(RtDevScene sc, WfState 
     float entry = 0.0f, exit_ = 0.0f, root_exit = 0.0f;
     while (true) {
         // ---- refill idle lanes
-        const bool need = !live && !exhausted;
-        const unsigned long long m = __ballot(need);
-        if (m) {
-            const int leader = __ffsll((long long)m) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
-            base = __shfl(base, leader);
-            if (need) {
-                e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                if (e >= n) {
-                    exhausted = true;
+        if (!live && !exhausted) {
+            e = wave_next_index(fetch, lane);
+            if (e >= n) {
+                exhausted = true;
+            } else {
+                o = ld3(ldf4(rays + 2 * (size_t)e));
+                d = ld3(ldf4(rays + 2 * (size_t)e + 1));
+                if (COUNT) c.v[RT_CNT_RAY]++;
+                if (bbox_hit(sc, o, d, entry, exit_)) {
+                    root_exit = exit_;
+                    node = 0;
+                    sp = 0;
+                    live = true;
                 } else {
-                    o = ld3(ldf4(rays + 2 * (size_t)e));
-                    d = ld3(ldf4(rays + 2 * (size_t)e + 1));
-                    if (COUNT) c.v[RT_CNT_RAY]++;
-                    if (bbox_hit(sc, o, d, entry, exit_)) {
-                        root_exit = exit_;
-                        node = 0;
-                        sp = 0;
-                        live = true;
-                    } else {
-                        *reinterpret_cast<float4 *>(st.hits + e) = miss_record();
-                    }
+                    store_miss(st, e);
                 }
             }
         }
@@ -363,98 +313,25 @@ __global__ void __launch_bounds__(WF_BLOCK) wf_trace_dyn(RtDevScene sc, WfState 
         if (COUNT) c.v[RT_CNT_NODE]++;
         while ((nd.y & 3u) != RT_LEAF_TAG) {
             const uint32_t axis = nd.y & 3u;
-            const float split = as_float(nd.x);
-            const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
-            const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
-            uint32_t near_c = node + 1, far_c = nd.y >> 2;
-            if (oax >= split) {
-                near_c = nd.y >> 2;
-                far_c = node + 1;
-            }
-            const float t = (split - oax) / dax;
-            if (t >= exit_ || t < 0) {
-                node = near_c;
-            } else if (t <= entry) {
-                node = far_c;
-            } else {
-                if (COUNT && sp >= RT_REF_STACK) c.v[RT_CNT_DEEP_PUSH]++;
-                stk.put(sp, far_c, t);
-                ++sp;
-                node = near_c;
-                exit_ = t;
-            }
+            const bool pushed = kd_split_step<KD_IEEE_DIV, KD_PLAIN>(nd, kd_axis(axis, o), kd_axis(axis, d), 0.0f, 0.0f,
+                                                                     node, entry, exit_, sp, stk);
+            if (COUNT && pushed && sp - 1 >= RT_REF_STACK) c.v[RT_CNT_DEEP_PUSH]++;
             nd = *reinterpret_cast<const uint2 *>(sc.nodes + 2 * (size_t)node);
             if (COUNT) c.v[RT_CNT_NODE]++;
         }
         // ---- leaf (rt/trace_ray.cuh:115-172)
-        const int count = (int)(nd.y >> 2);
-        int best = -1;
+        const uint32_t count = nd.y >> 2;
         float bx = 0.0f, by = 0.0f, bz = 0.0f;
-        if (count > 0) {
-            const uint32_t e0 = nd.x, e1 = nd.x + (uint32_t)count;
-            float smallest = exit_;
-            for (uint32_t k = e0; k < e1; k += 2) {
-                const bool two = k + 1 < e1;
-                if (COUNT) c.v[RT_CNT_TRI] += two ? 2 : 1;
-                const RtF4 A0 = ldf4(sc.isect_a + k);
-                const RtF4 A1 = ldf4(sc.isect_a + (two ? k + 1 : k));
-                const float dn0 = d.x * A0.x + d.y * A0.y + d.z * A0.z;
-                const float dn1 = d.x * A1.x + d.y * A1.y + d.z * A1.z;
-                const float s0 = (A0.w - (o.x * A0.x + o.y * A0.y + o.z * A0.z)) / dn0;
-                const float s1 = (A1.w - (o.x * A1.x + o.y * A1.y + o.z * A1.z)) / dn1;
-                const bool p0 = dn0 != 0 && s0 >= 0.00001f && s0 < smallest;
-                const bool p1 = two && dn1 != 0 && s1 >= 0.00001f && s1 < smallest;
-                RtF4 B0, C0, D0, B1, C1, D1;
-                uint2 R0, R1;
-                if (p0) {
-                    B0 = ldf4(&sc.isect_bary[k].b);
-                    C0 = ldf4(&sc.isect_bary[k].c);
-                    D0 = ldf4(&sc.isect_bary[k].d);
-                    R0 = *reinterpret_cast<const uint2 *>(&sc.isect_bary[k].rd);
-                }
-                if (p1) {
-                    B1 = ldf4(&sc.isect_bary[k + 1].b);
-                    C1 = ldf4(&sc.isect_bary[k + 1].c);
-                    D1 = ldf4(&sc.isect_bary[k + 1].d);
-                    R1 = *reinterpret_cast<const uint2 *>(&sc.isect_bary[k + 1].rd);
-                }
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const bool p = j == 0 ? p0 : p1;
-                    const float s = j == 0 ? s0 : s1;
-                    if (!p || !(s < smallest)) continue;
-                    const RtF4 B = j == 0 ? B0 : B1, C = j == 0 ? C0 : C1, D = j == 0 ? D0 : D1;
-                    const uint2 R = j == 0 ? R0 : R1;
-                    const float rd = as_float(R.x);
-                    const float px = o.x + d.x * s, py = o.y + d.y * s, pz = o.z + d.z * s;
-                    const float v2x = px - B.x, v2y = py - B.y, v2z = pz - B.z;
-                    const float d20 = v2x * C.x + v2y * C.y + v2z * C.z;
-                    const float d21 = v2x * D.x + v2y * D.y + v2z * D.z;
-                    const float cy = (D.w * d20 - C.w * d21) * rd;
-                    const float cz = (B.w * d21 - C.w * d20) * rd;
-                    const float cx = 1.0f - cy - cz;
-                    if (rt_bary_inside(cx, cy, cz)) {
-                        smallest = s;
-                        best = (int)R.y;
-                        bx = cx;
-                        by = cy;
-                        bz = cz;
-                    }
-                }
-            }
-        }
+        const int best = count > 0 ? leaf_scan_pairs<COUNT>(sc, nd.x, nd.x + count, o, d, exit_, bx, by, bz, c) : -1;
         if (best >= 0) {
             if (COUNT) c.v[RT_CNT_HIT]++;
-            *reinterpret_cast<float4 *>(st.hits + e) = make_float4(__int_as_float(best), bx, by, bz);
+            store_hit(st, e, best, bx, by, bz);
             live = false;
         } else if (sp == 0) {
-            *reinterpret_cast<float4 *>(st.hits + e) = miss_record();
+            store_miss(st, e);
             live = false;
         } else {
-            --sp;
-            node = stk.node_at(sp);
-            entry = stk.entry_at(sp);
-            exit_ = sp > 0 ? stk.entry_at(sp - 1) : root_exit;
+            kd_pop(stk, sp, root_exit, node, entry, exit_);
         }
     }
     if (COUNT) flush_counters(c, counters);
@@ -502,23 +379,15 @@ __global__ void __launch_bounds__(WF_TBLOCK, WF_TRACE_WAVES) wf_trace_coop(RtDev
     while (true) {
         const unsigned long long tf = COUNT ? __builtin_amdgcn_s_memtime() : 0ull;
         // ---- refill idle lanes (dynamic ray fetch)
-        const bool need = !r.live && !exhausted;
-        const unsigned long long m = __ballot(need);
-        if (m) {
-            const int leader = __ffsll((long long)m) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(fetch, (uint32_t)__popcll(m));
-            base = __shfl(base, leader);
-            if (need) {
-                e = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                if (e >= n) {
-                    exhausted = true;
-                    if (timeline && e == n) atomicMin(timeline + 1, __builtin_amdgcn_s_memrealtime());
-                } else {
-                    if (COUNT) c.v[RT_CNT_RAY]++;
-                    if (!coop_begin(sc, r, ld3(ldf4(rays + 2 * (size_t)e)), ld3(ldf4(rays + 2 * (size_t)e + 1))))
-                        *reinterpret_cast<float4 *>(st.hits + e) = miss_record();
-                }
+        if (!r.live && !exhausted) {
+            e = wave_next_index(fetch, lane);
+            if (e >= n) {
+                exhausted = true;
+                if (timeline && e == n) atomicMin(timeline + 1, __builtin_amdgcn_s_memrealtime());
+            } else {
+                if (COUNT) c.v[RT_CNT_RAY]++;
+                if (!coop_begin(sc, r, ld3(ldf4(rays + 2 * (size_t)e)), ld3(ldf4(rays + 2 * (size_t)e + 1))))
+                    store_miss(st, e);
             }
         }
         if (COUNT && lane == 0) c.v[RT_CNT_T_FETCH] += __builtin_amdgcn_s_memtime() - tf;
@@ -533,7 +402,7 @@ __global__ void __launch_bounds__(WF_TBLOCK, WF_TRACE_WAVES) wf_trace_coop(RtDev
         // wave — leave the loop and finish them wide (below)
         if (wide_lanes > 0 && __any(exhausted) && __popcll(__ballot(r.live)) <= wide_lanes) break;
         if (coop_round<COUNT>(sc, r, stk, w, cap, postpone, tri, bx, by, bz, c))
-            *reinterpret_cast<float4 *>(st.hits + e) = make_float4(__int_as_float(tri), bx, by, bz);
+            store_hit(st, e, tri, bx, by, bz);
     }
     // finish the wave's remaining rays one at a time with all 64 lanes
     // (wide_resume) instead of letting the longest run alone at one lane's pace
@@ -550,7 +419,7 @@ __global__ void __launch_bounds__(WF_TBLOCK, WF_TRACE_WAVES) wf_trace_coop(RtDev
             int tri = -1;
             float bx = 0.0f, by = 0.0f, bz = 0.0f;
             wide_resume<COUNT>(sc, r, owner, so, W, tri, bx, by, bz, c);
-            if (lane == owner) *reinterpret_cast<float4 *>(st.hits + e) = make_float4(__int_as_float(tri), bx, by, bz);
+            if (lane == owner) store_hit(st, e, tri, bx, by, bz);
         }
     }
     if (timeline && lane == 0) atomicMin(timeline + 2, ~__builtin_amdgcn_s_memrealtime());

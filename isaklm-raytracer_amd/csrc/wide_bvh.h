@@ -189,7 +189,8 @@ __device__ __forceinline__ bool wide_smin(const RtDevScene &sc, Vec3D o, Vec3D d
 // more than 63 nodes ahead costs a memory round trip.  A leaf's search for T*
 // (kd_bounded's fast leaf) compares 64 entries per round trip.  Same
 // decisions, same arithmetic, same result as kd_bounded — every lane computes
-// it; call with all 64 lanes active.
+// it; call with all 64 lanes active.  (The split step and the pop are
+// kd_bounded's own functions; the leaf visit is written out: see kd_bounded.)
 #define WSM_KD_BLOCK 64 // nodes per block (512 B of the wave's LDS: the start of wide_smin's lists, dead by then)
 
 // COUNT (lane 0's counters, as kd_bounded's): RT_CNT_NODE, RT_CNT_TRI, RT_CNT_HIT.
@@ -214,36 +215,15 @@ __device__ __forceinline__ int kd_bounded_wave(const RtDevScene &sc, const Vec3D
         return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
     };
     float exit_ = root_exit;
-    const float yx = rt_recip_guard(d.x), yy = rt_recip_guard(d.y), yz = rt_recip_guard(d.z);
+    const Vec3D y = rt_v3(rt_recip_guard(d.x), rt_recip_guard(d.y), rt_recip_guard(d.z));
     int sp = 0;
     uint32_t node = 0;
     while (true) {
         uint2 nd = fetch(node);
         while ((nd.y & 3u) != RT_LEAF_TAG) {
             const uint32_t axis = nd.y & 3u;
-            const float split = as_float(nd.x);
-            const float oax = axis == 0 ? o.x : (axis == 1 ? o.y : o.z);
-            const float dax = axis == 0 ? d.x : (axis == 1 ? d.y : d.z);
-            const float yax = axis == 0 ? yx : (axis == 1 ? yy : yz);
-            uint32_t near_c = node + 1, far_c = nd.y >> 2;
-            if (oax >= split) { // ray_behind_plane (:174-188)
-                near_c = nd.y >> 2;
-                far_c = node + 1;
-            }
-            const float t = rt_div_by(split - oax, dax, yax); // intersect_plane (:190-210)
-            if (t >= exit_ || t < 0) {
-                node = near_c;
-            } else if (t <= entry) {
-                node = far_c;
-            } else if (t <= s_min) { // the near side holds no hit: its leaves' exits are <= t
-                node = far_c;
-                entry = t;
-            } else {
-                stk.put(sp, far_c, t);
-                ++sp;
-                node = near_c;
-                exit_ = t;
-            }
+            kd_split_step<KD_DEVICE_DIV, KD_BOUNDED>(nd, kd_axis(axis, o), kd_axis(axis, d), kd_axis(axis, y), s_min, node,
+                                                     entry, exit_, sp, stk);
             nd = fetch(node);
         }
         const uint32_t count = nd.y >> 2;
@@ -291,10 +271,7 @@ __device__ __forceinline__ int kd_bounded_wave(const RtDevScene &sc, const Vec3D
             }
         }
         if (sp == 0) return -1;
-        --sp;
-        node = stk.node_at(sp);
-        entry = stk.entry_at(sp);
-        exit_ = sp > 0 ? stk.entry_at(sp - 1) : root_exit;
+        kd_pop(stk, sp, root_exit, node, entry, exit_);
     }
 }
 

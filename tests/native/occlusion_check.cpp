@@ -1,6 +1,6 @@
 // occlusion_check.cpp — host restatement of the occlusion query (rt_occluded:
 // csrc/query.hip rt_occluded_kernel, csrc/bvh_trace.h occluded_bvh /
-// kd_bounded_s / trace_s) checked against its definition on a real scene:
+// kd_bounded<false, true> / trace_s) checked against its definition on a real scene:
 //
 //   occluded(ray, tmax) = trace_ray (rt/trace_ray.cuh:244-318) hits && s < tmax
 //
@@ -53,7 +53,7 @@ struct Fast : NoObserver {
     void tstar_leaf() { ++n; }
 } g_fast;
 
-// bvh_trace.h kd_bounded_s (s_min = -inf, tstar = -1: trace_s): the device's division, and its fall-back
+// bvh_trace.h kd_bounded with WANT_S (s_min = -inf, tstar = -1: trace_s): the device's division, and its fall-back
 // to the whole leaf where a T* entry does not pass
 Hit device_descent(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float entry, float root_exit, float s_min, int tstar)
 {
