@@ -538,6 +538,9 @@ typedef struct RtOptions {
                               * RtDeviations.wide_overflows counts them) */
 #define RT_DEBUG_COUNT_LONG_ONLY 128 /* measurement (RT_TRAVERSAL_BOUNDED_COUNTED calls): only the long-path kernel
                                      * counts, so the counters hold the deep bounces' work alone */
+#define RT_DEBUG_BUDGET1 256 /* tests of the path kernel's parked bound queries (RT_TRAVERSAL_BOUNDED_COUNTED calls): a
+                             * wave parks its unfinished queries after one step of work instead of the shipped
+                             * budget (identical results and counters); added within ABI 12, no struct changed */
 /* (calls with RT_DEBUG_CALL_LOG, _LONG_LOG or _SERIAL_* are never coalesced) */
 
 /* Per-call kernel timing of the last rt_render on this device with

@@ -201,12 +201,13 @@ __device__ __forceinline__ float bvh_bound(const RtDevScene &sc, Vec3D o, Vec3D 
 #define RT_BVH4 1 // trace_bvh's s_min query on the 4-wide collapse (0: the binary tree)
 #endif
 //
-// The query's state between two node steps is (cur, sp, best) plus the stack
-// (LDS / spill area): PARK stops the query before its cap-th node step and
-// hands that state back (returns false), and a later call with resume picks
-// it up where it stopped — the same visiting order, the same s_min.  The
-// whole-call finisher parks a lane's long query so that the rest of its wave
-// goes on with shading instead of waiting for that one lane (wf_finish_bvh).
+// The query's state between two bodies — node steps or leaf visits — is (cur,
+// sp, best, tk) plus the stack (LDS / spill area): bvh4_query_budget stops a
+// query there, hands that state back (returns false), and a later call with
+// resume picks it up where it stopped — the same visiting order, the same
+// s_min.  The whole-call finisher parks its lanes' unfinished queries so that
+// the rest of the wave goes on with shading instead of waiting (wf_finish_bvh).
+// (bvh4_query runs a query to its end and returns the result in pk.best / pk.tk.)
 struct BvhPark {
     uint32_t cur;
     int sp;
@@ -263,34 +264,17 @@ __device__ __forceinline__ uint32_t bvh4_children(const RtDevScene &sc, uint32_t
     return t0 != INFINITY ? r0 : RT_BVH_EMPTY;
 }
 
-template <bool COUNT, bool PARK, typename STACK>
-__device__ __forceinline__ bool bvh4_query(const RtDevScene &sc, Vec3D o, Vec3D d, float best0, STACK &stk, Cnt &cn,
-                                           int cap, bool resume, BvhPark &pk)
+template <bool COUNT, typename STACK>
+__device__ __forceinline__ void bvh4_query(const RtDevScene &sc, Vec3D o, Vec3D d, float best0, STACK &stk, Cnt &cn,
+                                           BvhPark &pk)
 {
     const RtSlab sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, sc.bvh_scale));
     int sp = 0;
     uint32_t cur = 0; // the root (always an inner node)
     float best = best0;
     int tk = -1;
-    if (PARK && resume) {
-        sp = pk.sp;
-        cur = pk.cur;
-        best = pk.best;
-        tk = pk.tk;
-    }
-    int steps = 0;
     while (true) {
         while (!(cur & RT_BVH_LEAF)) {
-            if (PARK) {
-                if (steps >= cap) {
-                    pk.cur = cur;
-                    pk.sp = sp;
-                    pk.best = best;
-                    pk.tk = tk;
-                    return false;
-                }
-                ++steps;
-            }
             if (COUNT) cn.v[RT_CNT_B_BVH_NODE]++;
             const uint32_t next = bvh4_children(sc, cur, sl, best, stk, sp);
             cur = next != RT_BVH_EMPTY ? next : bvh_pop(stk, sp, best);
@@ -304,7 +288,79 @@ __device__ __forceinline__ bool bvh4_query(const RtDevScene &sc, Vec3D o, Vec3D 
     }
     pk.best = best;
     pk.tk = tk;
-    return true;
+}
+
+// The parked query scheduled and budgeted by the WAVE's work (wf_finish_bvh, WF_BVH_BUDGET).  A cap on a lane's
+// own node steps does not bound what its wave executes: leaf visits were never counted, and in a while-while
+// loop the node runs of lanes whose leaves fall at different places do not line up — the wave ran 16 node-phase
+// iterations and 5 leaf visits per call for lanes that took at most 6 node steps each (profiles/query_budget/).
+// Here the wave executes one BODY at a time: a node step for the lanes that hold a node, or a leaf visit for the
+// lanes that hold a leaf, whichever has more lanes waiting (a tie: the node step) — the others wait with their
+// state untouched.  Every body counts once, in a scalar (the loop's conditions are ballots: wave-uniform over
+// the lanes in this call), and at `budget` bodies every lane whose query is unfinished parks: in front of a node
+// step or in front of a leaf visit (cur is then the leaf's reference, and the resumed lane goes on with its scan).
+//
+// Progress rule: whatever the budget, a lane with an unfinished query executes at least one body of its own in
+// every call.  New rays join the wave in every trip and always start at a node, so a majority (or a node phase
+// that always ran first) could starve a lane parked at a leaf for ever.  Hence the first bodies of a call are
+// owed: a leaf visit if any lane entered at a leaf, then a node step if any lane entered at a node — neither
+// subject to the budget.  A query therefore takes no more calls than it has bodies.
+//
+// A lane's own sequence of node steps, leaf visits and pops is bvh4_query's: only where it waits and where it
+// pauses moves.  Returns true with the result in pk.best / pk.tk, false with the state in pk.
+template <bool COUNT, typename STACK>
+__device__ __forceinline__ bool bvh4_query_budget(const RtDevScene &sc, Vec3D o, Vec3D d, float best0, STACK &stk,
+                                                  Cnt &cn, const int budget, bool resume, BvhPark &pk)
+{
+    const RtSlab sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, sc.bvh_scale));
+    int sp = 0;
+    uint32_t cur = 0; // the root (always an inner node)
+    float best = best0;
+    int tk = -1;
+    if (resume) {
+        sp = pk.sp;
+        cur = pk.cur;
+        best = pk.best;
+        tk = pk.tk;
+    }
+    auto leaf_visit = [&]() {
+        const uint32_t first = (cur & ~RT_BVH_LEAF) >> 3, end = first + (cur & 7u) + 1u;
+        if (COUNT) cn.v[RT_CNT_B_BVH_TRI] += end - first;
+        leaf_scan_min<COUNT>(sc.bvh_a, sc.bvh_bary, first, end, o, d, best, tk, cn);
+        cur = bvh_pop(stk, sp, best);
+    };
+    int bodies = 0;                                       // (wave-uniform, as everything that steers the loop)
+    bool lead = __any((cur & RT_BVH_LEAF) != 0u) != 0;    // lanes resumed at a leaf (never RT_BVH_EMPTY: that is done)
+    bool owed = __any(!(cur & RT_BVH_LEAF)) != 0;         // lanes entered at a node
+    while (true) {
+        const bool node = !(cur & RT_BVH_LEAF), leaf = !node && cur != RT_BVH_EMPTY;
+        const unsigned long long nm = __ballot(node), lm = __ballot(leaf);
+        if (!(nm | lm)) break;
+        bool leaf_phase;
+        if (lead) {
+            leaf_phase = true;
+            lead = false;
+        } else if (owed) {
+            leaf_phase = false;
+            owed = false;
+        } else {
+            if (bodies >= budget) break;
+            leaf_phase = __popcll(lm) > __popcll(nm);
+        }
+        if (leaf_phase) {
+            if (leaf) leaf_visit();
+        } else if (node) {
+            if (COUNT) cn.v[RT_CNT_B_BVH_NODE]++;
+            const uint32_t next = bvh4_children(sc, cur, sl, best, stk, sp);
+            cur = next != RT_BVH_EMPTY ? next : bvh_pop(stk, sp, best);
+        }
+        ++bodies;
+    }
+    pk.cur = cur;
+    pk.sp = sp;
+    pk.best = best;
+    pk.tk = tk;
+    return cur == RT_BVH_EMPTY;
 }
 
 // (tstar: the triangle whose test alone set s_min — kd_bounded's fast leaf —, else -1; tk: its BVH slot,
@@ -314,7 +370,7 @@ __device__ __forceinline__ float bvh4_bound(const RtDevScene &sc, Vec3D o, Vec3D
                                             int &tstar, int &tk)
 {
     BvhPark pk;
-    (void)bvh4_query<COUNT, false>(sc, o, d, best, stk, cn, 0, false, pk);
+    bvh4_query<COUNT>(sc, o, d, best, stk, cn, pk);
     tk = pk.tk;
     tstar = pk.tk >= 0 ? (int)sc.bvh_bary[pk.tk].tri : -1;
     return pk.best;
@@ -474,7 +530,7 @@ __device__ __forceinline__ int trace_bvh(const RtDevScene &sc, const Vec3D o, co
     return h;
 }
 
-// trace_bvh with the s_min query parked after `cap` node steps (bvh4_query), and with the KD descent of
+// trace_bvh with the s_min query parked after `budget` bodies of its wave (bvh4_query_budget), and with the KD descent of
 // a ray the certificate does not cover put off where the caller asks (defer_kd).  Returns RT_PARK_DONE
 // with the hit in `hit` (-1: miss) — trace_bvh's result, bit for bit —, RT_PARK_BVH (pk holds the query's
 // state) or RT_PARK_KD (pk.best / pk.tk hold s_min and its slot: only the descent is left); call again
@@ -484,7 +540,7 @@ __device__ __forceinline__ int trace_bvh(const RtDevScene &sc, const Vec3D o, co
 #define RT_PARK_KD 2
 template <bool COUNT, typename STACK>
 __device__ __forceinline__ int trace_bvh_park(const RtDevScene &sc, const Vec3D o, const Vec3D d, int &hit, float &hbx,
-                                              float &hby, float &hbz, STACK &stk, Cnt &c, int cap, int resume,
+                                              float &hby, float &hbz, STACK &stk, Cnt &c, int budget, int resume,
                                               bool defer_kd, BvhPark &pk)
 {
     if (COUNT && resume == RT_PARK_DONE) c.v[RT_CNT_RAY]++;
@@ -496,7 +552,7 @@ __device__ __forceinline__ int trace_bvh_park(const RtDevScene &sc, const Vec3D 
     int tstar = -1;
     if (rt_bounded_ray(o, d, sc.split_vals, sc.split_off)) {
         if (resume != RT_PARK_KD) {
-            if (!bvh4_query<COUNT, true>(sc, o, d, exit_, stk, c, cap, resume == RT_PARK_BVH, pk)) return RT_PARK_BVH;
+            if (!bvh4_query_budget<COUNT>(sc, o, d, exit_, stk, c, budget, resume == RT_PARK_BVH, pk)) return RT_PARK_BVH;
             if (!(pk.best < root_exit)) return RT_PARK_DONE;
             if (kd_certified<COUNT>(sc, o, d, entry, root_exit, pk.best, pk.tk, hit, hbx, hby, hbz, c))
                 return RT_PARK_DONE;

@@ -6,6 +6,8 @@
 //   kd_descent   bvh_trace.h kd_bounded over rt_kernels.h kd_split_step / kd_pop, statement for statement
 //   bvh4_smin    bvh_trace.h bvh4_query + bvh4_children + leaf_scan_min
 //   bvh_bound    bvh_trace.h bvh_bound (the binary tree; the 4-wide query's cross-check)
+//   Bvh4Walk     bvh4_smin one body at a time; wave_call_budget: bvh_trace.h bvh4_query_budget over a wave's lanes
+//                (wave_call_lane_cap: the per-lane cap it replaced)
 //   kd_resume    coop_trace.h kd_origin_frontier's replay, cell_of its grid lookup
 //   bvh8         an 8-wide work model (experiments only)
 //
@@ -14,7 +16,7 @@
 // in one place.
 //
 // Not product code: shared by tests/native/{bvh_trace,kd_cert,wide_smin,
-// occlusion}_check.cpp and tools/{deep_ray_work,kd_jump_sim}.cpp; nothing the
+// occlusion,trip_budget}_check.cpp and tools/{deep_ray_work,kd_jump_sim,trip_model}.cpp; nothing the
 // library is built from includes it.
 #pragma once
 #include <math.h>
@@ -318,6 +320,203 @@ inline Smin bvh4_smin(const rt_host::PreparedHost &h, Vec3D o, Vec3D d, float be
 {
     NoObserver none;
     return bvh4_smin(h, o, d, best, none);
+}
+
+// ---------------------------------------------------------------- the parked queries of a wave (wf_finish_bvh)
+// bvh4_smin one body at a time: the state the device keeps between two bodies (BvhPark's cur, sp, best, tk and
+// the stack), a node step (bvh4_children + pop) and a leaf visit (leaf_scan_min + pop) as bvh4_smin runs them.
+struct Bvh4Walk {
+    const rt_host::PreparedHost *h = nullptr;
+    Vec3D o, d;
+    RtSlab sl;
+    struct B { uint32_t ref; float tn; };
+    std::vector<B> stk;
+    uint32_t cur = RT_BVH_EMPTY;
+    float best = 0.0f;
+    int tk = -1;
+    long long bodies = 0, trips = 0; // bodies of its own so far; wave calls it took part in
+
+    void start(const rt_host::PreparedHost &hh, Vec3D oo, Vec3D dd, float best0)
+    {
+        h = &hh;
+        o = oo;
+        d = dd;
+        sl = rt_slab(o, d, rt_ray_margin(o.x, o.y, o.z, hh.bvh_scale));
+        stk.clear();
+        cur = 0;
+        best = best0;
+        tk = -1;
+        bodies = trips = 0;
+    }
+    bool done() const { return cur == RT_BVH_EMPTY; }
+    bool at_node() const { return !(cur & RT_BVH_LEAF); }
+    bool at_leaf() const { return (cur & RT_BVH_LEAF) && cur != RT_BVH_EMPTY; }
+    int leaf_chunks() const { return (int)((cur & 7u) + 1u + 3u) / 4; } // leaf_scan_min's 4-entry chunks
+    uint32_t pop()
+    {
+        while (!stk.empty()) {
+            const B e = stk.back();
+            stk.pop_back();
+            if (e.tn <= best) return e.ref;
+        }
+        return RT_BVH_EMPTY;
+    }
+    void node_step()
+    {
+        ++bodies;
+        const float *f = reinterpret_cast<const float *>(&h->bvh4[8 * (size_t)cur]);
+        const uint32_t *rf = reinterpret_cast<const uint32_t *>(f + 24);
+        float t[4];
+        uint32_t r[4];
+        for (int k = 0; k < 4; ++k) {
+            r[k] = rf[k];
+            if (!rt_bvh_box(f[k], f[4 + k], f[8 + k], f[12 + k], f[16 + k], f[20 + k], sl, best, t[k])) t[k] = INFINITY;
+        }
+        auto cswap = [&](int a, int b) {
+            if (t[b] < t[a]) {
+                std::swap(t[a], t[b]);
+                std::swap(r[a], r[b]);
+            }
+        };
+        cswap(0, 1);
+        cswap(2, 3);
+        cswap(0, 2);
+        cswap(1, 3);
+        cswap(1, 2);
+        for (int k = 3; k >= 1; --k)
+            if (t[k] != INFINITY) stk.push_back(B{r[k], t[k]});
+        cur = t[0] != INFINITY ? r[0] : pop();
+    }
+    void leaf_visit()
+    {
+        ++bodies;
+        const uint32_t first = (cur & ~RT_BVH_LEAF) >> 3, end = first + (cur & 7u) + 1u;
+        for (uint32_t e = first; e < end; ++e) { // leaf_scan_min
+            float s, b[3];
+            if (!rt_tri_plane(h->bvh_a[e], o, d, INFINITY, s) || !(s <= best)) continue;
+            const bool lt = s < best;
+            if (!lt && tk < 0) continue;
+            const RtIsectBary &R = h->bvh_bary[e];
+            if (!rt_tri_bary(R.b, R.c, R.d, bitsf(R.rd), o, d, s, b[0], b[1], b[2])) continue;
+            if (lt) {
+                best = s;
+                tk = (int)e;
+            } else {
+                tk = TK_TIE;
+            }
+        }
+        cur = pop();
+    }
+};
+
+// what one call of a wave's parked queries executed: the bodies the WAVE ran (a node-phase iteration or a leaf
+// visit, whichever lanes take part; chunks: the longest leaf of each visit in 4-entry chunks), the bodies of
+// the lanes' own, the lanes in the call and those whose query ended in it
+struct WaveTrip {
+    long long node_bodies = 0, leaf_bodies = 0, leaf_chunks = 0, lane_bodies = 0, lanes = 0, finished = 0;
+};
+
+// bvh_trace.h bvh4_query_budget over the lanes of a wave (the unfinished queries in `q`): one body at a time — a
+// node step for the lanes at a node or a leaf visit for the lanes at a leaf, whichever are more (a tie: the node
+// step) —, one count per body; the first bodies are owed (a leaf visit if a lane entered at a leaf, then a node
+// step if a lane entered at a node), and from `budget` bodies on every unfinished lane parks
+inline WaveTrip wave_call_budget(std::vector<Bvh4Walk *> &q, int budget)
+{
+    WaveTrip w;
+    auto count = [&](auto pred) {
+        int n = 0;
+        for (Bvh4Walk *l : q) n += pred(*l) ? 1 : 0;
+        return n;
+    };
+    for (Bvh4Walk *l : q) {
+        ++l->trips;
+        ++w.lanes;
+    }
+    long long bodies = 0;
+    bool lead = count([](const Bvh4Walk &l) { return l.at_leaf(); }) > 0;
+    bool owed = count([](const Bvh4Walk &l) { return l.at_node(); }) > 0;
+    while (true) {
+        const int nn = count([](const Bvh4Walk &l) { return l.at_node(); });
+        const int nl = count([](const Bvh4Walk &l) { return l.at_leaf(); });
+        if (nn + nl == 0) break;
+        bool leaf_phase;
+        if (lead) {
+            leaf_phase = true;
+            lead = false;
+        } else if (owed) {
+            leaf_phase = false;
+            owed = false;
+        } else {
+            if (bodies >= budget) break;
+            leaf_phase = nl > nn;
+        }
+        if (leaf_phase) {
+            int chunks = 0;
+            for (Bvh4Walk *l : q)
+                if (l->at_leaf()) {
+                    chunks = std::max(chunks, l->leaf_chunks());
+                    l->leaf_visit();
+                    ++w.lane_bodies;
+                }
+            ++w.leaf_bodies;
+            w.leaf_chunks += chunks;
+        } else {
+            for (Bvh4Walk *l : q)
+                if (l->at_node()) {
+                    l->node_step();
+                    ++w.lane_bodies;
+                }
+            ++w.node_bodies;
+        }
+        ++bodies;
+    }
+    for (Bvh4Walk *l : q) w.finished += l->done();
+    return w;
+}
+
+// bvh_trace.h bvh4_query<PARK> over the lanes of a wave: the while-while loop with a cap on each lane's own node
+// steps (the rule before the budget); a lane parks in front of its (cap + 1)-th node step, leaf visits are free
+inline WaveTrip wave_call_lane_cap(std::vector<Bvh4Walk *> &q, int cap)
+{
+    WaveTrip w;
+    std::vector<int> steps(q.size(), 0);
+    std::vector<char> parked(q.size(), 0);
+    for (Bvh4Walk *l : q) {
+        ++l->trips;
+        ++w.lanes;
+    }
+    while (true) {
+        while (true) { // the node phase: until every lane holds a leaf, is done or is parked
+            bool ran = false;
+            for (size_t i = 0; i < q.size(); ++i) {
+                if (parked[i] || !q[i]->at_node()) continue;
+                if (steps[i] >= cap) {
+                    parked[i] = 1;
+                    continue;
+                }
+                ++steps[i];
+                q[i]->node_step();
+                ++w.lane_bodies;
+                ran = true;
+            }
+            if (!ran) break;
+            ++w.node_bodies;
+        }
+        int chunks = 0;
+        bool leaf = false;
+        for (size_t i = 0; i < q.size(); ++i) {
+            if (parked[i] || !q[i]->at_leaf()) continue;
+            chunks = std::max(chunks, q[i]->leaf_chunks());
+            q[i]->leaf_visit();
+            ++w.lane_bodies;
+            leaf = true;
+        }
+        if (!leaf) break;
+        ++w.leaf_bodies;
+        w.leaf_chunks += chunks;
+    }
+    for (Bvh4Walk *l : q) w.finished += l->done();
+    return w;
 }
 
 // bvh_trace.h bvh_bound: the same query on the binary tree (best alone)

@@ -620,7 +620,7 @@ int launch_whole_now(Workspace &w, const WholeCall &c)
     st.chk = check_mask == 0xFFFFFFFFu ? nullptr : w.chk + 3 * (size_t)w.chk_cap * (size_t)par;
     st.chk_cap = w.chk_cap;
     st.chk_ctr = w.chk_ctr + par;
-    st.chk_fault = (debug & RT_DEBUG_CHECK_FAULT) ? 1 : 0;
+    st.chk_fault = ((debug & RT_DEBUG_CHECK_FAULT) ? 1 : 0) | ((debug & RT_DEBUG_BUDGET1) ? WF_DEBUG_BUDGET1 : 0);
     // debug (RT_DEBUG_LONG_LOG): every deep sample's claim / end time and bounces
     if ((debug & RT_DEBUG_LONG_LOG) && !w.long_log_buf &&
         hipMalloc((void **)&w.long_log_buf, 8 * 4 * 65536) != hipSuccess) {

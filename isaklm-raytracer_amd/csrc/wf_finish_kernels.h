@@ -107,9 +107,8 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
     uint32_t quiet_trips = 0;               // (lane 0) idle loop trips in a row with no wf_long path running
     uint32_t idle_trips = 0;                // (lane 0) idle loop trips in a row
     bool seated = false;                    // (lane 0) holds a linger seat
-#if WF_BVH_PARK
-    // a lane whose s_min query ran WF_BVH_PARK node steps parks it (its state in LDS, the stack in
-    // place) and resumes it in the wave's next loop trip: the rest of the wave shades meanwhile
+    // a wave whose s_min queries ran WF_BVH_BUDGET bodies parks the unfinished ones (a lane's state in LDS, the
+    // stack in place) and resumes them in its next loop trip: the rest of the wave shades meanwhile
     __shared__ uint32_t s_pk_cur[WF_BLOCK];
     __shared__ int s_pk_sp[WF_BLOCK];
     __shared__ float s_pk_best[WF_BLOCK];
@@ -119,7 +118,6 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
     // walk a descent alone: the pending descents run together, in a trip where WF_KD_PEND_MIN lanes wait
     // for theirs or no lane of the wave has anything else to do.
     int parked = RT_PARK_DONE;
-#endif
     while (true) {
         // (fresh) pixels whose passes are done are let go — unless a later chained call queued
         // passes for them meanwhile: those run next, in the pixel's order (its state is this lane's).
@@ -373,7 +371,7 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
         quiet_trips = 0;
         idle_trips = 0;
         bool to_long = false;
-#if WF_BVH_PARK && RT_KD_CERT
+#if RT_KD_CERT
         const unsigned long long kd_pend = __ballot(active && parked == RT_PARK_KD);
         const bool run_kd = kd_pend != 0ull && (__popcll(kd_pend) >= WF_KD_PEND_MIN ||
                                                 __ballot(active && parked != RT_PARK_KD) == 0ull);
@@ -382,11 +380,13 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
         if (active) {
 #endif
             float bx = 0.0f, by = 0.0f, bz = 0.0f;
-#if WF_BVH_PARK
             int hit;
             BvhPark pk{0u, 0, 0.0f, -1};
             if (parked != RT_PARK_DONE) pk = BvhPark{s_pk_cur[tid], s_pk_sp[tid], s_pk_best[tid], s_pk_tk[tid]};
-            parked = trace_bvh_park<COUNT>(sc, p.ro, p.rd, hit, bx, by, bz, stk, c, WF_BVH_PARK, parked, true, pk);
+            // (the budget is a compile-time constant in the product instantiation: no scalar joins its hot set.
+            // Tests run the counting instantiation at budget 1, RT_DEBUG_BUDGET1.)
+            const int budget = COUNT && (WF_COLD(st).chk_fault & WF_DEBUG_BUDGET1) ? 1 : WF_BVH_BUDGET;
+            parked = trace_bvh_park<COUNT>(sc, p.ro, p.rd, hit, bx, by, bz, stk, c, budget, parked, true, pk);
             const bool done = parked == RT_PARK_DONE;
             if (!done) {
                 s_pk_cur[tid] = pk.cur;
@@ -394,10 +394,6 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
                 s_pk_best[tid] = pk.best;
                 s_pk_tk[tid] = pk.tk;
             }
-#else
-            const int hit = trace_bvh<COUNT>(sc, p.ro, p.rd, bx, by, bz, stk, c);
-            const bool done = true;
-#endif
             // run-time exactness guard: a deterministic sample of the rays, with the
             // bounded result, is queued for wf_check's plain KD re-trace
             if (!COUNT && st.chk && done) {
@@ -412,7 +408,7 @@ __global__ void __launch_bounds__(WF_BLOCK, WAVES) wf_finish_bvh(RtDevScene sc, 
                     const uint32_t i = wave_append(cs.chk_ctr, rec);
                     if (rec && i < cs.chk_cap) {
                         cs.chk[3 * (size_t)i] =
-                            RtF4{p.ro.x, p.ro.y, p.ro.z, __int_as_float(cs.chk_fault ? (hit >= 0 ? hit ^ 1 : 0) : hit)};
+                            RtF4{p.ro.x, p.ro.y, p.ro.z, __int_as_float((cs.chk_fault & 1) ? (hit >= 0 ? hit ^ 1 : 0) : hit)};
                         cs.chk[3 * (size_t)i + 1] = RtF4{p.rd.x, p.rd.y, p.rd.z, bx};
                         cs.chk[3 * (size_t)i + 2] = RtF4{by, bz, 0.0f, 0.0f};
                     }

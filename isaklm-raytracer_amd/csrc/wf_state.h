@@ -89,11 +89,13 @@ static_assert(WF_BLOCK % WF_TBLOCK == 0 && WF_TBLOCK % 64 == 0, "WF_TBLOCK must 
                             // drain), and the least an unchained call gets: alone on the chip, that one's grid
                             // follows its records up to the spill area's lanes (wf_check_grid.h)
 #endif
-#ifndef WF_BVH_PARK
-#define WF_BVH_PARK 6 // wf_finish_bvh: BVH node steps per loop trip before a lane's query parks (0: never; re-swept
-                      // after round 6's VALU cuts: 4 / 5 / 6 / 7 / 8 / 12 / 16 = 723-727 / 733 / 738-742 / 739-741 /
-                      // 712-731 / 715 / 699-700 Msamples/s, profiles/r06/ab/ ab16-ab17)
+#ifndef WF_BVH_BUDGET
+#define WF_BVH_BUDGET 14 // wf_finish_bvh: bodies — node steps and leaf visits, each for whichever lanes hold one — the
+                         // WAVE executes per loop trip before every unfinished s_min query parks (bvh_trace.h
+                         // bvh4_query_budget; it replaced WF_BVH_PARK = 6, a cap on each lane's own node steps under
+                         // which the wave ran ~21 bodies per trip; 12 / 14 / 18: profiles/query_budget/)
 #endif
+#define WF_DEBUG_BUDGET1 2 // WfState.chk_fault bit (RtOptions.debug RT_DEBUG_BUDGET1): the counting finisher's budget is 1
 #ifndef WF_KD_PEND_MIN
 #define WF_KD_PEND_MIN 4 // wf_finish_bvh: lanes of a wave waiting for their KD descent (rays the T* certificate does
                          // not cover, RT_PARK_KD) before a loop trip runs them; fewer wait — unless the wave has
@@ -283,7 +285,7 @@ struct WfState {
     uint32_t *chk_ctr;
     uint32_t chk_mask;
     uint32_t chk_cap; // records per parity (more are dropped: RT_DEV_CHK_DROP)
-    int chk_fault; // (RT_DEBUG_CHECK_FAULT, tests: record a wrong result for every checked ray)
+    int chk_fault; // (bit 0: RT_DEBUG_CHECK_FAULT, tests: record a wrong result for every checked ray; WF_DEBUG_BUDGET1)
     int debug_quit; // (RT_DEBUG_LONG_QUIT, tests: wf_long leaves at once, as by its safety net)
     // wf_long's bounded bounces (whole-call mode): the wave-wide s_min query and the wave-run bounded KD
     // traversal (wide_bvh.h).  0: off (the wide KD traversal), 1: on, 2: on with list capacity 1

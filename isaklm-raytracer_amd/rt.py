@@ -185,6 +185,7 @@ DEBUG_CALL_LOG, DEBUG_LONG_LOG, DEBUG_CHECK_FAULT, DEBUG_LONG_QUIT = 1, 2, 4, 8 
 DEBUG_SERIAL_LONG_FIRST, DEBUG_SERIAL_FIN_FIRST = 16, 32  # (tests: serialised dispatch in either order)
 DEBUG_COUNT_LONG_ONLY = 128  # (measurement: a counted call in which only wf_long counts, tools/wide_rounds.py)
 DEBUG_WIDE_CAP1 = 64  # (tests: wf_long's wave-wide s_min query overflows at once; deviation_stats wide_overflows)
+DEBUG_BUDGET1 = 256  # (tests: a counted call's finisher parks its s_min queries after one body of the wave's work)
 TRIANGLE_BYTES = 152
 NODE_BYTES = 20
 COUNTER_NAMES = ["node", "tri", "hit", "texel", "nee", "sample", "skip", "ray", "watchdog", "maxdepth"]
