@@ -28,6 +28,8 @@
 // host/reproject_host.cpp: the overlap rule
 bool rt_rp_frames_overlap(const void *src_fb, const void *src_sq, const void *src_count, const void *dst_fb,
                           const void *dst_sq, const void *dst_count, size_t n);
+// ... and rt_reproject_sampler's rule for its two samplers (nullptr, or the text of the rule that failed)
+const char *rt_rp_resolve_samplers(const RtSampler *src, const RtSampler *dst, RtDevSampler *s, RtDevSampler *d);
 
 static thread_local std::string g_error;
 
@@ -1116,6 +1118,36 @@ int rt_render_aov(rt_scene_t scene, Camera cam, int width, int height, const RtA
                        stream);
 }
 
+int rt_sample_aov(rt_scene_t scene, const RtSampler *sampler, long long n, const RtAovBuffers *b, const RtQueryOptions *opt)
+{
+    RtQueryOptions o;
+    if (!b) { rt_set_error("rt_sample_aov: null buffers"); return RT_E_INVALID; }
+    if (misaligned(b->depth, 4) || misaligned(b->normal, 4) || misaligned(b->albedo, 4) || misaligned(b->triangle, 4)) {
+        rt_set_error("rt_sample_aov: misaligned buffer");
+        return RT_E_INVALID;
+    }
+    if (!count_ok("rt_sample_aov", n)) return RT_E_INVALID;
+    RtDevSampler smp;
+    if (const char *why = rt_sampler_resolve(sampler, n, &smp)) {
+        rt_set_error("rt_sample_aov: %s", why);
+        return RT_E_INVALID;
+    }
+    if (smp.kind == RT_SAMPLER_HEMISPHERE) {
+        rt_set_error("rt_sample_aov: a hemisphere sampler has no centre ray");
+        return RT_E_INVALID;
+    }
+    const int rc = query_options("rt_sample_aov", scene, opt, &o);
+    if (rc != RT_OK) return rc;
+    if (n == 0) return RT_OK;
+    if (!b->depth && !b->normal && !b->albedo && !b->triangle && !o.stats_device) return RT_OK; // nothing asked for
+    rt_register_shutdown();
+    hipStream_t stream = (hipStream_t)o.stream;
+    return launch_done("rt_sample_aov",
+                       rt_launch_sample_aov(scene->dev, smp, n, b->depth, b->normal, b->albedo, b->triangle, o.traversal,
+                                            o.stats_device, stream),
+                       stream);
+}
+
 int rt_tonemap(G_Buffer g, uint8_t *rgba, int w, int h, void *stream)
 {
     if (!rgba || !g.frame_buffer || !g.sample_count || w <= 0 || h <= 0) {
@@ -1148,76 +1180,129 @@ int rt_convergence(const float *radiance, const float *sq_luminance, const int *
 }
 
 // ---------------- denoising (denoise.hip; rt_denoise_host and the default options: host/denoise_host.cpp) ----------------
-int rt_denoise(G_Buffer g, const RtAovBuffers *aov, int width, int height, float *rgb_out, const RtDenoiseOptions *opt)
+// rt_denoise and rt_denoise_sampler (who; sampler: NULL, or the frame's sampler — its size is the frame's, and an
+// EQUIRECT one makes the x axis periodic)
+static int denoise(const char *who, G_Buffer g, const RtAovBuffers *aov, const RtSampler *sampler, int width, int height,
+                   float *rgb_out, const RtDenoiseOptions *opt)
 {
     RtDnParams prm;
     if (!rt_dn_resolve(opt, &prm)) {
-        rt_set_error("rt_denoise: option out of range (iterations 1..%d, normal_log2 1..%d, demodulate -1..1, "
-                     "sigmas finite and >= 0)", RT_DN_MAX_ITERATIONS, RT_DN_MAX_NORMAL_LOG2);
+        rt_set_error("%s: option out of range (iterations 1..%d, normal_log2 1..%d, demodulate -1..1, "
+                     "sigmas finite and >= 0)", who, RT_DN_MAX_ITERATIONS, RT_DN_MAX_NORMAL_LOG2);
         return RT_E_INVALID;
     }
     if (!g.frame_buffer || !g.squared_luminance || !g.sample_count || !rgb_out || !aov || !aov->depth ||
         !aov->normal || (prm.demodulate && !aov->albedo)) {
-        rt_set_error("rt_denoise: null G_Buffer array, AOV buffer or output");
+        rt_set_error("%s: null G_Buffer array, AOV buffer or output", who);
         return RT_E_INVALID;
     }
     if (misaligned(rgb_out, 4) || misaligned(aov->depth, 4) || misaligned(aov->normal, 4) || misaligned(aov->albedo, 4)) {
-        rt_set_error("rt_denoise: misaligned buffer");
+        rt_set_error("%s: misaligned buffer", who);
         return RT_E_INVALID;
     }
-    const int rc = frame_size_ok("rt_denoise", width, height, 1);
+    int wrap_x = 0;
+    if (sampler) {
+        RtDevSampler smp;
+        if (const char *why = rt_sampler_resolve_frame(sampler, &smp)) {
+            rt_set_error("%s: %s", who, why);
+            return RT_E_INVALID;
+        }
+        width = smp.width;
+        height = smp.height;
+        wrap_x = smp.kind == RT_SAMPLER_EQUIRECT;
+    }
+    const int rc = frame_size_ok(who, width, height, 1);
     if (rc != RT_OK) return rc;
     hipStream_t stream = (hipStream_t)(opt ? opt->stream : nullptr);
-    const int jr = join_status(stream, "rt_denoise"); // chained renders' deep-path tails first, as rt_tonemap
+    const int jr = join_status(stream, who); // chained renders' deep-path tails first, as rt_tonemap
     if (jr != RT_OK) return jr;
     rt_register_shutdown();
-    return launch_done("rt_denoise",
+    return launch_done(who,
                        rt_launch_denoise(g.frame_buffer, g.squared_luminance, g.sample_count, aov->depth, aov->normal,
-                                         aov->albedo, width, height, rgb_out, prm, stream),
+                                         aov->albedo, width, height, rgb_out, prm, stream, wrap_x),
                        stream);
+}
+
+int rt_denoise(G_Buffer g, const RtAovBuffers *aov, int width, int height, float *rgb_out, const RtDenoiseOptions *opt)
+{
+    return denoise("rt_denoise", g, aov, nullptr, width, height, rgb_out, opt);
+}
+
+int rt_denoise_sampler(G_Buffer g, const RtAovBuffers *aov, const RtSampler *sampler, float *rgb_out,
+                       const RtDenoiseOptions *opt)
+{
+    if (!sampler) { rt_set_error("rt_denoise_sampler: null sampler"); return RT_E_INVALID; }
+    return denoise("rt_denoise_sampler", g, aov, sampler, 0, 0, rgb_out, opt);
 }
 
 // ---------------- temporal reprojection (reproject.hip; rt_reproject_host and the default options:
 // host/reproject_host.cpp) ----------------
-int rt_reproject(G_Buffer src, const RtAovBuffers *sa, Camera src_cam, const RtAovBuffers *da, Camera dst_cam, int width,
-                 int height, G_Buffer dst, const RtReprojectOptions *opt)
+// rt_reproject and rt_reproject_sampler (who) on the two views' frame constants; model: RT_SAMPLER_PINHOLE ..
+// RT_SAMPLER_ORTHO
+static int reproject(const char *who, G_Buffer src, const RtAovBuffers *sa, const RtDevCamera &src_cam,
+                     const RtAovBuffers *da, const RtDevCamera &dst_cam, int model, const RtRpLens &lens, int width,
+                     int height, G_Buffer dst, const RtReprojectOptions *opt, const RtRpParams &prm)
 {
-    RtRpParams prm;
-    if (!rt_rp_resolve(opt, &prm)) {
-        rt_set_error("rt_reproject: option out of range (max_history 1..%d, match_triangle -1..1, depth_tol finite "
-                     "and >= 0, normal_min in (-1, 1])", RT_RP_MAX_HISTORY);
-        return RT_E_INVALID;
-    }
     if (!src.frame_buffer || !src.squared_luminance || !src.sample_count || !dst.frame_buffer ||
         !dst.squared_luminance || !dst.sample_count || !sa || !da || !sa->depth || !sa->normal || !da->depth ||
         !da->normal) {
-        rt_set_error("rt_reproject: null G_Buffer array or AOV buffer");
+        rt_set_error("%s: null G_Buffer array or AOV buffer", who);
         return RT_E_INVALID;
     }
     if (misaligned(sa->depth, 4) || misaligned(sa->normal, 4) || misaligned(sa->triangle, 4) ||
         misaligned(da->depth, 4) || misaligned(da->normal, 4) || misaligned(da->triangle, 4) ||
         misaligned(opt ? opt->stats_device : nullptr, 8)) {
-        rt_set_error("rt_reproject: misaligned buffer");
+        rt_set_error("%s: misaligned buffer", who);
         return RT_E_INVALID;
     }
-    const int rc = frame_size_ok("rt_reproject", width, height, 1);
+    const int rc = frame_size_ok(who, width, height, 1);
     if (rc != RT_OK) return rc;
     if (rt_rp_frames_overlap(src.frame_buffer, src.squared_luminance, src.sample_count, dst.frame_buffer,
                              dst.squared_luminance, dst.sample_count, (size_t)width * height)) {
-        rt_set_error("rt_reproject: dst's arrays overlap src's (the call is a gather)");
+        rt_set_error("%s: dst's arrays overlap src's (the call is a gather)", who);
         return RT_E_INVALID;
     }
     hipStream_t stream = (hipStream_t)(opt ? opt->stream : nullptr);
-    const int jr = join_status(stream, "rt_reproject"); // chained renders' deep-path tails first, as rt_tonemap
+    const int jr = join_status(stream, who); // chained renders' deep-path tails first, as rt_tonemap
     if (jr != RT_OK) return jr;
     rt_register_shutdown();
     const RtRpFrame sf = {src.frame_buffer, src.squared_luminance, src.sample_count, sa->depth, sa->normal, sa->triangle};
-    return launch_done("rt_reproject",
-                       rt_launch_reproject(sf, rt_rp_camera(src_cam), da->depth, da->normal, da->triangle,
-                                           rt_rp_camera(dst_cam), width, height, prm, dst.frame_buffer,
-                                           dst.squared_luminance, dst.sample_count, opt ? opt->stats_device : nullptr,
-                                           stream),
+    return launch_done(who,
+                       rt_launch_reproject(sf, src_cam, da->depth, da->normal, da->triangle, dst_cam, width, height, prm,
+                                           dst.frame_buffer, dst.squared_luminance, dst.sample_count,
+                                           opt ? opt->stats_device : nullptr, stream, model, lens),
                        stream);
+}
+
+static bool reproject_options_ok(const char *who, const RtReprojectOptions *opt, RtRpParams *prm)
+{
+    if (rt_rp_resolve(opt, prm)) return true;
+    rt_set_error("%s: option out of range (max_history 1..%d, match_triangle -1..1, depth_tol finite "
+                 "and >= 0, normal_min in (-1, 1])", who, RT_RP_MAX_HISTORY);
+    return false;
+}
+
+int rt_reproject(G_Buffer src, const RtAovBuffers *sa, Camera src_cam, const RtAovBuffers *da, Camera dst_cam, int width,
+                 int height, G_Buffer dst, const RtReprojectOptions *opt)
+{
+    RtRpParams prm;
+    if (!reproject_options_ok("rt_reproject", opt, &prm)) return RT_E_INVALID;
+    return reproject("rt_reproject", src, sa, rt_rp_camera(src_cam), da, rt_rp_camera(dst_cam), RT_SAMPLER_PINHOLE,
+                     RtRpLens{0.0f, 0.0f, 0.0f, 0.0f}, width, height, dst, opt, prm);
+}
+
+int rt_reproject_sampler(G_Buffer src, const RtAovBuffers *sa, const RtSampler *src_sampler, const RtAovBuffers *da,
+                         const RtSampler *dst_sampler, G_Buffer dst, const RtReprojectOptions *opt)
+{
+    RtRpParams prm;
+    if (!reproject_options_ok("rt_reproject_sampler", opt, &prm)) return RT_E_INVALID;
+    RtDevSampler ss, ds;
+    if (const char *why = rt_rp_resolve_samplers(src_sampler, dst_sampler, &ss, &ds)) {
+        rt_set_error("rt_reproject_sampler: %s", why);
+        return RT_E_INVALID;
+    }
+    return reproject("rt_reproject_sampler", src, sa, ss.cam, da, ds.cam, ds.kind, rt_rp_lens(ss, ds), ds.width, ds.height,
+                     dst, opt, prm);
 }
 
 int rt_tonemap_rgb(const float *rgb, uint8_t *rgba, int w, int h, void *stream)

@@ -1,4 +1,4 @@
-// denoise.hip — rt_denoise's kernels and rt_tonemap_rgb.
+// denoise.hip — rt_denoise's and rt_denoise_sampler's kernels and rt_tonemap_rgb.
 //
 // The filter is defined in denoise_math.h (the text host/denoise_host.cpp
 // compiles too); this file only maps it onto the GPU:
@@ -28,6 +28,8 @@
 
 namespace {
 
+// WRAP_X: the x axis is periodic (denoise_math.h; rt_denoise_sampler's EQUIRECT frames)
+template <bool WRAP_X>
 __global__ void __launch_bounds__(256) dn_prepare_kernel(const Vec3D *fb, const float *sq, const int *count,
                                                          const float *depth, const float *normal,
                                                          const float *albedo, int width, int height, int tiles_x,
@@ -39,14 +41,14 @@ __global__ void __launch_bounds__(256) dn_prepare_kernel(const Vec3D *fb, const 
     const int p = y * width + x;
     RtDn4 s, g;
     float gz;
-    rt_dn_prepare_pixel(fb, sq, count, depth, normal, albedo, width, height, x, y, demodulate, &s, &g, &gz);
+    rt_dn_prepare_pixel<WRAP_X>(fb, sq, count, depth, normal, albedo, width, height, x, y, demodulate, &s, &g, &gz);
     state[p] = s;
     guide[p] = g;
     slope[p] = gz;
 }
 
 // FINAL: the last level — remodulate and store 3 floats per pixel into rgb_out (state_out unused)
-template <bool FINAL>
+template <bool FINAL, bool WRAP_X>
 __global__ void __launch_bounds__(256) dn_filter_kernel(const RtDn4 *__restrict__ state_in,
                                                         const RtDn4 *__restrict__ guide,
                                                         const float *__restrict__ slope, int width, int height,
@@ -57,7 +59,7 @@ __global__ void __launch_bounds__(256) dn_filter_kernel(const RtDn4 *__restrict_
     const int y = (int)(blockIdx.x / (unsigned)tiles_x) * DN_TILE_H + threadIdx.y;
     if (x >= width || y >= height) return;
     const int p = y * width + x;
-    const RtDn4 s = rt_dn_filter_pixel(state_in, guide, slope, width, height, x, y, step, prm);
+    const RtDn4 s = rt_dn_filter_pixel<WRAP_X>(state_in, guide, slope, width, height, x, y, step, prm);
     if (FINAL) {
         const Vec3D c = rt_dn_remodulate(s, rt_dn_demodulator(albedo, (size_t)p, prm.demodulate));
         float *o = rgb_out + 3 * (size_t)p;
@@ -129,33 +131,43 @@ bool size_workspace(DenoiseWorkspace &w, size_t n)
     return true;
 }
 
+// the prepare pass and the levels on `stream` (the workspace is sized and `stream` waits for its last user)
+template <bool WRAP_X>
+void launch_levels(DenoiseWorkspace &w, const Vec3D *fb, const float *sq, const int *count, const float *depth,
+                   const float *normal, const float *albedo, int width, int height, float *rgb_out,
+                   const RtDnParams &prm, hipStream_t stream)
+{
+    const dim3 block(DN_TILE_W, DN_TILE_H);
+    // (a 1-D grid of tiles, row by row: up to 2^31 / 256 + width / 32 + height / 8 blocks, within the x limit)
+    const int tiles_x = (width + DN_TILE_W - 1) / DN_TILE_W;
+    const dim3 grid((unsigned)((long long)tiles_x * ((height + DN_TILE_H - 1) / DN_TILE_H)));
+    hipLaunchKernelGGL(dn_prepare_kernel<WRAP_X>, grid, block, 0, stream, fb, sq, count, depth, normal, albedo, width, height,
+                       tiles_x, prm.demodulate, w.state[0], w.guide, w.slope);
+    for (int s = 0; s < prm.iterations; ++s) {
+        const RtDn4 *in = w.state[s & 1];
+        if (s + 1 < prm.iterations)
+            hipLaunchKernelGGL((dn_filter_kernel<false, WRAP_X>), grid, block, 0, stream, in, w.guide, w.slope, width, height,
+                               tiles_x, 1 << s, prm, w.state[(s + 1) & 1], albedo, rgb_out);
+        else
+            hipLaunchKernelGGL((dn_filter_kernel<true, WRAP_X>), grid, block, 0, stream, in, w.guide, w.slope, width, height,
+                               tiles_x, 1 << s, prm, (RtDn4 *)nullptr, albedo, rgb_out);
+    }
+}
+
 } // namespace
 
 // ---- launchers (called by abi.hip) ----
 int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const float *depth, const float *normal,
                       const float *albedo, int width, int height, float *rgb_out, const RtDnParams &prm,
-                      hipStream_t stream)
+                      hipStream_t stream, int wrap_x)
 {
     std::lock_guard<std::mutex> g(g_denoise.mu);
     DenoiseWorkspace *slot = g_denoise.current();
     if (!slot) return -1;
     DenoiseWorkspace &w = *slot;
     if (!size_workspace(w, (size_t)width * height) || !w.serial.wait_on(stream)) return -1;
-    const dim3 block(DN_TILE_W, DN_TILE_H);
-    // (a 1-D grid of tiles, row by row: up to 2^31 / 256 + width / 32 + height / 8 blocks, within the x limit)
-    const int tiles_x = (width + DN_TILE_W - 1) / DN_TILE_W;
-    const dim3 grid((unsigned)((long long)tiles_x * ((height + DN_TILE_H - 1) / DN_TILE_H)));
-    hipLaunchKernelGGL(dn_prepare_kernel, grid, block, 0, stream, fb, sq, count, depth, normal, albedo, width, height,
-                       tiles_x, prm.demodulate, w.state[0], w.guide, w.slope);
-    for (int s = 0; s < prm.iterations; ++s) {
-        const RtDn4 *in = w.state[s & 1];
-        if (s + 1 < prm.iterations)
-            hipLaunchKernelGGL(dn_filter_kernel<false>, grid, block, 0, stream, in, w.guide, w.slope, width, height,
-                               tiles_x, 1 << s, prm, w.state[(s + 1) & 1], albedo, rgb_out);
-        else
-            hipLaunchKernelGGL(dn_filter_kernel<true>, grid, block, 0, stream, in, w.guide, w.slope, width, height,
-                               tiles_x, 1 << s, prm, (RtDn4 *)nullptr, albedo, rgb_out);
-    }
+    if (wrap_x) launch_levels<true>(w, fb, sq, count, depth, normal, albedo, width, height, rgb_out, prm, stream);
+    else launch_levels<false>(w, fb, sq, count, depth, normal, albedo, width, height, rgb_out, prm, stream);
     return w.serial.record(stream) ? 0 : -1;
 }
 

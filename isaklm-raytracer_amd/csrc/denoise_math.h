@@ -82,8 +82,19 @@ RT_HD float rt_dn_axis_slope(float z, bool has_next, float z_next, bool has_prev
     return use_next ? a : b;
 }
 
+// x + dx on a periodic x axis (an equirectangular frame: longitude -pi and +pi are neighbours), for any dx
+RT_HD int rt_dn_wrap(int xx, int width)
+{
+    xx %= width;
+    return xx < 0 ? xx + width : xx;
+}
+
 // The prepare pass of pixel (x, y): the filter state (irradiance, variance of
 // its mean luminance), the packed guides (normal, depth) and the depth slope.
+// WRAP_X (rt_denoise_sampler on an EQUIRECT frame): every x neighbour is taken
+// modulo width instead of clamped or dropped; rows never wrap (the poles are
+// edges).  WRAP_X = false is rt_denoise's filter.
+template <bool WRAP_X = false>
 RT_HD void rt_dn_prepare_pixel(const Vec3D *fb, const float *sq, const int *count, const float *depth,
                                const float *normal, const float *albedo, int width, int height, int x, int y,
                                int demodulate, RtDn4 *state, RtDn4 *guide, float *slope)
@@ -110,14 +121,23 @@ RT_HD void rt_dn_prepare_pixel(const Vec3D *fb, const float *sq, const int *coun
     guide->y = normal[3 * p + 1];
     guide->z = normal[3 * p + 2];
     guide->w = z;
-    const float gx = rt_dn_axis_slope(z, x + 1 < width, x + 1 < width ? depth[p + 1] : 0.0f, x > 0,
-                                      x > 0 ? depth[p - 1] : 0.0f);
+    float gx;
+    if constexpr (WRAP_X) {
+        const size_t row = (size_t)y * width;
+        gx = rt_dn_axis_slope(z, true, depth[row + (x + 1 < width ? x + 1 : 0)], true,
+                              depth[row + (x > 0 ? x - 1 : width - 1)]);
+    } else {
+        gx = rt_dn_axis_slope(z, x + 1 < width, x + 1 < width ? depth[p + 1] : 0.0f, x > 0,
+                              x > 0 ? depth[p - 1] : 0.0f);
+    }
     const float gy = rt_dn_axis_slope(z, y + 1 < height, y + 1 < height ? depth[p + width] : 0.0f, y > 0,
                                       y > 0 ? depth[p - width] : 0.0f);
     *slope = gx > gy ? gx : gy;
 }
 
-// One a-trous level at pixel (x, y), tap spacing `step`: the new state.
+// One a-trous level at pixel (x, y), tap spacing `step`: the new state.  WRAP_X: as rt_dn_prepare_pixel — the
+// tap order stays dy, then dx, from -2 to 2; taps that alias one pixel (2 * step >= width) are taken again.
+template <bool WRAP_X = false>
 RT_HD RtDn4 rt_dn_filter_pixel(const RtDn4 *state, const RtDn4 *guide, const float *slope, int width, int height,
                                int x, int y, int step, const RtDnParams &prm)
 {
@@ -130,7 +150,8 @@ RT_HD RtDn4 rt_dn_filter_pixel(const RtDn4 *state, const RtDn4 *guide, const flo
         yy = yy < 0 ? 0 : (yy >= height ? height - 1 : yy);
         for (int dx = -1; dx <= 1; ++dx) {
             int xx = x + dx;
-            xx = xx < 0 ? 0 : (xx >= width ? width - 1 : xx);
+            if constexpr (WRAP_X) xx = xx < 0 ? width - 1 : (xx >= width ? 0 : xx);
+            else xx = xx < 0 ? 0 : (xx >= width ? width - 1 : xx);
             const float g = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
             vbar += g * state[yy * width + xx].w;
         }
@@ -149,8 +170,12 @@ RT_HD RtDn4 rt_dn_filter_pixel(const RtDn4 *state, const RtDn4 *guide, const flo
         if (yy < 0 || yy >= height) continue;
         const int ay = dy < 0 ? -dy : dy;
         for (int dx = -2; dx <= 2; ++dx) {
-            const int xx = x + step * dx;
-            if (xx < 0 || xx >= width) continue;
+            int xx = x + step * dx;
+            if constexpr (WRAP_X) {
+                xx = rt_dn_wrap(xx, width);
+            } else {
+                if (xx < 0 || xx >= width) continue;
+            }
             const int ax = dx < 0 ? -dx : dx;
             const int q = yy * width + xx;
             const RtDn4 sq_ = state[q];

@@ -11,6 +11,7 @@
 //
 //   rt_trace_rays   rays from a buffer      -> hit (+ surface) records
 //   rt_render_aov   rays from the camera    -> planar AOV buffers
+//   rt_sample_aov   a sampler's centre rays -> planar AOV buffers
 // and a second kernel of the same shape for the any-hit question:
 //   rt_occluded     rays + tmax from buffers -> one byte per ray
 // and a third that runs the renderer's whole path loop on the caller's rays:
@@ -96,6 +97,14 @@ struct SamplerRays { // sampler_math.h: element e's next ray, drawn from the ele
     __device__ __forceinline__ void done(uint32_t e, int samples, int accumulate) const
     {
         if (count) count[e] = (accumulate ? count[e] : 0) + samples;
+    }
+};
+struct CentreRays { // sampler_math.h: element e's centre ray of an image sampler (rt_sample_aov), nothing drawn
+    RtDevSampler smp;
+    __device__ __forceinline__ void load(uint32_t e, Vec3D &o, Vec3D &d) const
+    {
+        uint32_t st = 0; // (unused: a centre ray draws nothing)
+        rt_sampler_ray<true>(smp, e, st, o, d);
     }
 };
 struct CameraRays { // ray e = the centre of pixel (e % width, e / width), row 0 = bottom
@@ -715,6 +724,13 @@ int rt_launch_render_aov(const RtDevScene &sc, const RtDevCamera &cam, int width
     const AovSink sink{depth, normal, albedo, triangle};
     return launch_query(rt_query_kernel<CameraRays, AovSink>, sc, camera_source(cam, width, height), sink,
                         (long long)width * height, traversal, stats, stream);
+}
+
+int rt_launch_sample_aov(const RtDevScene &sc, const RtDevSampler &smp, long long n, float *depth, float *normal,
+                         float *albedo, int *triangle, int traversal, unsigned long long *stats, hipStream_t stream)
+{
+    const AovSink sink{depth, normal, albedo, triangle};
+    return launch_query(rt_query_kernel<CentreRays, AovSink>, sc, CentreRays{smp}, sink, n, traversal, stats, stream);
 }
 
 int rt_launch_camera_rays(const RtDevCamera &cam, int width, int height, float *rays, hipStream_t stream)

@@ -9,6 +9,7 @@
 struct RtDnParams; // denoise_math.h
 struct RtRpFrame;  // reproject_math.h
 struct RtRpParams;
+struct RtRpLens;
 struct RtDevSampler; // sampler_math.h
 struct RtCvParams;   // convergence_math.h
 
@@ -45,18 +46,22 @@ int rt_launch_sample_paths(const RtDevScene &sc, const RtDevSampler &smp, uint32
 int rt_launch_sampler_rays(const RtDevSampler &smp, uint32_t *rng, long long n, float *rays, hipStream_t stream);
 void rt_query_shutdown();
 
-// denoise.hip
+// denoise.hip (wrap_x: the x axis is periodic — rt_denoise_sampler's EQUIRECT frames)
 int rt_launch_denoise(const Vec3D *fb, const float *sq, const int *count, const float *depth, const float *normal,
                       const float *albedo, int width, int height, float *rgb_out, const RtDnParams &prm,
-                      hipStream_t stream);
+                      hipStream_t stream, int wrap_x);
 int rt_launch_tonemap_rgb(const float *rgb, RtUChar4 *out, int n, hipStream_t stream);
 void rt_denoise_shutdown();
 
-// reproject.hip
+// reproject.hip (model: RT_SAMPLER_PINHOLE .. RT_SAMPLER_ORTHO, the two cameras' model; lens: what the models
+// beside the pinhole read of the samplers)
 int rt_launch_reproject(const RtRpFrame &src, const RtDevCamera &src_cam, const float *dst_depth,
                         const float *dst_normal, const int *dst_triangle, const RtDevCamera &dst_cam, int width,
                         int height, const RtRpParams &prm, Vec3D *fb_out, float *sq_out, int *count_out,
-                        unsigned long long *stats, hipStream_t stream);
+                        unsigned long long *stats, hipStream_t stream, int model, const RtRpLens &lens);
+// query.hip: rt_sample_aov — the sampler's centre rays into the AOV buffers
+int rt_launch_sample_aov(const RtDevScene &sc, const RtDevSampler &smp, long long n, float *depth, float *normal,
+                         float *albedo, int *triangle, int traversal, unsigned long long *stats, hipStream_t stream);
 
 // convergence.hip
 int rt_launch_convergence(const float *radiance, const float *sq, const int *count, long long n, const RtCvParams &prm,

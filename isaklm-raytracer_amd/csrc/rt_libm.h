@@ -13,12 +13,14 @@
  * functions.  Both therefore use the code below: the argument is widened to
  * double, reduced with a Cody–Waite split of pi/2 and evaluated with the
  * (public-domain) fdlibm minimax kernels, then rounded once to float.  Only
- * IEEE-exact double operations (+ - * / floor frexp ldexp) are used, and every
- * translation unit that includes this header is compiled with
+ * IEEE-exact double operations (+ - * / floor frexp ldexp fabs copysign) are
+ * used, and every translation unit that includes this header is compiled with
  * -ffp-contract=off, so the result is the same bits on x86-64 (SSE2) and on
  * CDNA4 (v_*_f64).  The double result carries ~1e-16 relative error, so the
  * float result is the correctly rounded one except in vanishingly rare
  * hard-to-round cases (tests/test_libm.py measures this against glibc).
+ * rt_atan2f (the sampler frames' reprojection, reproject_math.h) is written
+ * the same way; tests/native/atan2_check.c measures it.
  *
  * This header is C99/C++/HIP: RT_LIBM_FN adds __host__ __device__ under hipcc.
  */
@@ -128,6 +130,76 @@ RT_LIBM_FN float rt_tanf(float xf)
     double r = rt_reduce_pio2((double)xf, &q);
     double s = rt_ksin(r), c = rt_kcos(r);
     return (float)((q & 1) ? -c / s : s / c);
+}
+
+/* fdlibm atan for a finite x >= 0: the argument is reduced onto one of
+ * atan(0.5), atan(1), atan(1.5), atan(inf) (each as a high and a low part) and
+ * the odd minimax polynomial aT runs on the remainder, |t| < 7/16.  Compares,
+ * + - * / only: nothing is reduced through an int. */
+RT_LIBM_FN double rt_katan(double x)
+{
+    const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01,
+                 aT2 = 1.42857142725034663711e-01, aT3 = -1.11111104054623557880e-01,
+                 aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
+                 aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02,
+                 aT8 = 4.97687799461593236017e-02, aT9 = -3.65315727442169155270e-02,
+                 aT10 = 1.62858201153657823623e-02;
+    double hi, lo, t;
+    if (x < 0.4375) {
+        hi = 0.0;
+        lo = 0.0;
+        t = x;
+    } else if (x < 0.6875) {
+        hi = 4.63647609000806093515e-01;
+        lo = 2.26987774529616870924e-17;
+        t = (2.0 * x - 1.0) / (2.0 + x);
+    } else if (x < 1.1875) {
+        hi = 7.85398163397448278999e-01;
+        lo = 3.06161699786838301793e-17;
+        t = (x - 1.0) / (x + 1.0);
+    } else if (x < 2.4375) {
+        hi = 9.82793723247329054082e-01;
+        lo = 1.39033110312309984516e-17;
+        t = (x - 1.5) / (1.0 + 1.5 * x);
+    } else {
+        hi = 1.57079632679489655800e+00;
+        lo = 6.12323399573676603587e-17;
+        t = -1.0 / x;
+    }
+    const double z = t * t;
+    const double w = z * z;
+    const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
+    const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
+    if (x < 0.4375) return t - t * (s1 + s2);
+    return hi - ((t * (s1 + s2) - lo) - t);
+}
+
+/* atan2f(y, x): the angle of the point (x, y) in [-pi, pi], C's atan2 on zeros
+ * and infinities (fdlibm e_atan2.c's cases); a NaN argument gives a NaN.  The
+ * quotient of two floats neither overflows nor underflows in double. */
+RT_LIBM_FN float rt_atan2f(float yf, float xf)
+{
+    const double PI_HI = 3.1415926535897931160e+00, PI_LO = 1.2246467991473531772e-16;
+    const double y = (double)yf, x = (double)xf;
+    if (x != x || y != y) return (float)NAN;
+    const double sy = copysign(1.0, y);
+    const int x_neg = copysign(1.0, x) < 0.0; /* (-0 counts: atan2(+-0, -0) = +-pi) */
+    const double ay = fabs(y), ax = fabs(x);
+    double z;
+    if (ay == 0.0) {
+        z = x_neg ? PI_HI : 0.0;
+    } else if (ax == 0.0) {
+        z = 0.5 * PI_HI;
+    } else if (ax == (double)INFINITY) {
+        if (ay == (double)INFINITY) z = x_neg ? 0.75 * PI_HI : 0.25 * PI_HI;
+        else z = x_neg ? PI_HI : 0.0;
+    } else if (ay == (double)INFINITY) {
+        z = 0.5 * PI_HI;
+    } else {
+        z = rt_katan(ay / ax);
+        if (x_neg) z = PI_HI - (z - PI_LO);
+    }
+    return (float)(sy * z);
 }
 
 /* natural log of a positive finite double: x = m * 2^e, m in [sqrt(1/2), sqrt(2)) */

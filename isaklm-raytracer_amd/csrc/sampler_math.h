@@ -83,6 +83,16 @@ inline const char *rt_sampler_resolve(const RtSampler *s, long long n, RtDevSamp
     return nullptr;
 }
 
+// A sampler that stands for a whole frame (rt_denoise_sampler, rt_reproject_sampler): an image kind without a
+// pixel list; nullptr, or the text of the rule that failed (host only)
+inline const char *rt_sampler_resolve_frame(const RtSampler *s, RtDevSampler *out)
+{
+    if (!s) return "null sampler";
+    if (s->kind == RT_SAMPLER_HEMISPHERE) return "a hemisphere sampler has no frame";
+    if (s->pixels_device) return "a pixel list is not a whole frame";
+    return rt_sampler_resolve(s, (long long)s->width * s->height, out);
+}
+
 // the branch-free orthonormal frame of n (Duff et al. 2017, "Building an Orthonormal Basis, Revisited")
 RT_HD void rt_sampler_frame(Vec3D n, Vec3D &t, Vec3D &b)
 {

@@ -286,6 +286,17 @@ def lib():
                                        Camera, i, i, G_Buffer, ctypes.POINTER(RtReprojectOptions)]
             L.rt_reproject_host.argtypes = [vp, vp, vp, vp, vp, vp, Camera, vp, vp, vp, Camera, i, i, vp, vp, vp, vp,
                                             ctypes.POINTER(RtReprojectOptions)]
+        if hasattr(L, "rt_sample_aov"):  # (added within ABI 12: an earlier ABI-12 library lacks it)
+            smp = ctypes.POINTER(RtSampler)
+            L.rt_sample_aov.argtypes = [vp, smp, ctypes.c_longlong, ctypes.POINTER(RtAovBuffers),
+                                        ctypes.POINTER(RtQueryOptions)]
+            L.rt_denoise_sampler.argtypes = [G_Buffer, ctypes.POINTER(RtAovBuffers), smp, vp,
+                                             ctypes.POINTER(RtDenoiseOptions)]
+            L.rt_denoise_sampler_host.argtypes = [vp, vp, vp, vp, vp, vp, smp, vp, ctypes.POINTER(RtDenoiseOptions)]
+            L.rt_reproject_sampler.argtypes = [G_Buffer, ctypes.POINTER(RtAovBuffers), smp, ctypes.POINTER(RtAovBuffers),
+                                               smp, G_Buffer, ctypes.POINTER(RtReprojectOptions)]
+            L.rt_reproject_sampler_host.argtypes = [vp, vp, vp, vp, vp, vp, smp, vp, vp, vp, smp, vp, vp, vp, vp,
+                                                    ctypes.POINTER(RtReprojectOptions)]
         L.rt_shutdown.restype = None
         L.rt_abi_version.restype = i
         if L.rt_abi_version() != ABI_VERSION:
@@ -996,6 +1007,45 @@ def render_aov(dscene, camera, width, height, traversal=None):
     return out
 
 
+def sample_aov_device(dscene, sampler, n, aov_ptrs, traversal=None, stream=None, stats_ptr=None, pixels_ptr=None):
+    """rt_sample_aov on device memory: `sampler` a Sampler (its pixel array is not used: pixels_ptr is the device
+    pointer to it), aov_ptrs (depth, normal, albedo, triangle) integer device pointers, any of them None."""
+    b = RtAovBuffers(*[_int_ptr(p) for p in aov_ptrs])
+    o = query_options(traversal, stream, _int_ptr(stats_ptr))
+    smp = sampler.struct(pixels_ptr, None)
+    check(lib().rt_sample_aov(dscene.prepared, ctypes.byref(smp), int(n), ctypes.byref(b), ctypes.byref(o)))
+
+
+def sample_aov(dscene, sampler, traversal=None, stats=False):
+    """rt_sample_aov: the first-hit feature buffers of an image sampler's centre rays, render_aov's dict — shaped
+    (H, W, ...) with row 0 = bottom for a whole frame, (n, ...) for a pixel list (out-of-frame entries miss: depth
+    inf, triangle -1); with stats=True also a dict of the call's counts (QUERY_STATS)."""
+    n = sampler.n
+    lead = (sampler.height, sampler.width) if sampler.pixels is None else (n,)
+    out = {"depth": np.zeros(lead, np.float32), "normal": np.zeros(lead + (3,), np.float32),
+           "albedo": np.zeros(lead + (3,), np.float32), "triangle": np.zeros(lead, np.int32)}
+    L = lib()
+    st = np.zeros(3, dtype=np.uint64)
+    with _SamplerArrays(sampler) as (d_pix, _), _DeviceBytes(n * 4) as d_depth, _DeviceBytes(n * 12) as d_normal, \
+            _DeviceBytes(n * 12) as d_albedo, _DeviceBytes(n * 4) as d_tri, _DeviceBytes(st.nbytes) as d_st:
+        if stats:
+            check(L.rt_memset(d_st, 0, st.nbytes))
+        sample_aov_device(dscene, sampler, n, (d_depth, d_normal, d_albedo, d_tri), traversal, None,
+                          d_st if stats else None, d_pix)
+        if n:
+            for name, d in (("depth", d_depth), ("normal", d_normal), ("albedo", d_albedo), ("triangle", d_tri)):
+                check(L.rt_download(_ptr(out[name]), d, out[name].nbytes))
+        if stats:
+            check(L.rt_download(_ptr(st), d_st, st.nbytes))
+    return (out, dict(zip(QUERY_STATS, (int(v) for v in st)))) if stats else out
+
+
+def _frame_sampler_struct(sampler):
+    """the RtSampler of a whole-frame call: a pixel list stays visible to the library (which refuses it) without
+    being uploaded"""
+    return sampler.struct(None if sampler.pixels is None else 4, None if sampler.points is None else 8)
+
+
 # ---------------------------------------------------------------- denoising
 def denoise_options(iterations=0, sigma_lum=0.0, sigma_depth=0.0, normal_log2=0, demodulate=True, stream=None):
     """RtDenoiseOptions; 0 = the library default (5 levels, sigma_lum 4, sigma_depth 1, normal_log2 7);
@@ -1015,10 +1065,32 @@ def denoise_device(g, aov_ptrs, width, height, out_ptr, **options):
     check(lib().rt_denoise(g, ctypes.byref(b), width, height, _int_ptr(out_ptr), ctypes.byref(o)))
 
 
+def denoise_sampler_device(g, aov_ptrs, sampler, out_ptr, **options):
+    """rt_denoise_sampler on device memory: denoise_device with a Sampler (a whole frame of an image kind) in place
+    of width and height; an equirect sampler's x axis is periodic."""
+    b = RtAovBuffers(_int_ptr(aov_ptrs[0]), _int_ptr(aov_ptrs[1]), _int_ptr(aov_ptrs[2]), None)
+    o = denoise_options(**options)
+    smp = _frame_sampler_struct(sampler)
+    check(lib().rt_denoise_sampler(g, ctypes.byref(b), ctypes.byref(smp), _int_ptr(out_ptr), ctypes.byref(o)))
+
+
 def denoise(gbuf, aov, **options):
     """rt_denoise: the denoised mean radiance of `gbuf` as (H, W, 3) float32, row 0 = bottom.  aov: the dict
     rt.render_aov returns (numpy arrays, uploaded here) or a dict of integer device pointers; keys depth,
     normal and — unless demodulate=False — albedo.  Options: denoise_options."""
+    return _denoise(gbuf, aov, None, options)
+
+
+def denoise_sampler(gbuf, aov, sampler, **options):
+    """rt_denoise_sampler: denoise for the frame of `sampler` (a Sampler of an image kind without a pixel list,
+    gbuf's size); aov: the dict rt.sample_aov returns, or device pointers.  For every kind but equirect the
+    result is denoise's; an equirect frame is filtered across the seam at longitude +-pi."""
+    if (sampler.width, sampler.height) != (gbuf.width, gbuf.height):
+        raise ValueError("the sampler's frame is not the G-buffer's")
+    return _denoise(gbuf, aov, sampler, options)
+
+
+def _denoise(gbuf, aov, sampler, options):
     W, H = gbuf.width, gbuf.height
     n = W * H
     L = lib()
@@ -1037,7 +1109,10 @@ def denoise(gbuf, aov, **options):
                 ptrs.append(d)
             else:
                 ptrs.append(aov.get(k))
-        denoise_device(gbuf.g, ptrs, W, H, d_out, **options)
+        if sampler is None:
+            denoise_device(gbuf.g, ptrs, W, H, d_out, **options)
+        else:
+            denoise_sampler_device(gbuf.g, ptrs, sampler, d_out, **options)
         _synchronize_stream(options.get("stream"))
         check(L.rt_download(_ptr(out), d_out, out.nbytes))
     return out
@@ -1047,10 +1122,22 @@ def denoise_host(fb, sq, count, depth, normal, albedo, **options):
     """rt_denoise_host: rt_denoise's arithmetic on the CPU, bit-identical to the GPU.  fb (H, W, 3), sq and
     count (H, W), depth (H, W), normal and albedo (H, W, 3) (albedo may be None with demodulate=False); the
     frame size is taken from depth's shape.  Returns (H, W, 3) float32."""
+    return _denoise_host(fb, sq, count, depth, normal, albedo, None, options)
+
+
+def denoise_sampler_host(fb, sq, count, depth, normal, albedo, sampler, **options):
+    """rt_denoise_sampler_host: denoise_host for the frame of `sampler` (the arrays must have its size),
+    bit-identical to denoise_sampler."""
+    return _denoise_host(fb, sq, count, depth, normal, albedo, sampler, options)
+
+
+def _denoise_host(fb, sq, count, depth, normal, albedo, sampler, options):
     depth = np.ascontiguousarray(depth, dtype=np.float32)
     if depth.ndim != 2:
         raise ValueError("depth must have shape (H, W)")
     H, W = depth.shape
+    if sampler is not None and (sampler.width, sampler.height) != (W, H):
+        raise ValueError("the sampler's frame is not the arrays'")
     n = W * H
 
     def arr(a, dtype, per):
@@ -1063,8 +1150,14 @@ def denoise_host(fb, sq, count, depth, normal, albedo, **options):
     albedo = None if albedo is None else arr(albedo, np.float32, 3)
     out = np.zeros((H, W, 3), np.float32)
     o = denoise_options(**options)
-    check(lib().rt_denoise_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(depth), _ptr(normal),
-                                None if albedo is None else _ptr(albedo), W, H, _ptr(out), ctypes.byref(o)))
+    if sampler is None:
+        check(lib().rt_denoise_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(depth), _ptr(normal),
+                                    None if albedo is None else _ptr(albedo), W, H, _ptr(out), ctypes.byref(o)))
+    else:
+        smp = _frame_sampler_struct(sampler)
+        check(lib().rt_denoise_sampler_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(depth), _ptr(normal),
+                                            None if albedo is None else _ptr(albedo), ctypes.byref(smp), _ptr(out),
+                                            ctypes.byref(o)))
     return out
 
 
@@ -1099,12 +1192,38 @@ def reproject_device(g_src, aov_src_ptrs, cam_src, aov_dst_ptrs, cam_dst, width,
 _RP_AOVS = (("depth", np.float32, 1), ("normal", np.float32, 3), ("triangle", np.int32, 1))
 
 
+def reproject_sampler_device(g_src, aov_src_ptrs, smp_src, aov_dst_ptrs, smp_dst, g_dst, **options):
+    """rt_reproject_sampler on device memory: reproject_device with two Samplers (whole frames of one image kind
+    and size) in place of the two cameras and the frame size."""
+    bs = RtAovBuffers(_int_ptr(aov_src_ptrs[0]), _int_ptr(aov_src_ptrs[1]), None, _int_ptr(aov_src_ptrs[2]))
+    bd = RtAovBuffers(_int_ptr(aov_dst_ptrs[0]), _int_ptr(aov_dst_ptrs[1]), None, _int_ptr(aov_dst_ptrs[2]))
+    if "stats" in options:
+        options = dict(options, stats=_int_ptr(options["stats"]))
+    o = reproject_options(**options)
+    ss, sd = _frame_sampler_struct(smp_src), _frame_sampler_struct(smp_dst)
+    check(lib().rt_reproject_sampler(g_src, ctypes.byref(bs), ctypes.byref(ss), ctypes.byref(bd), ctypes.byref(sd), g_dst,
+                                     ctypes.byref(o)))
+
+
+def reproject_sampler(gbuf_src, aov_src, smp_src, aov_dst, smp_dst, out=None, stats=False, **options):
+    """rt_reproject_sampler: reproject for a moved camera of any image kind — smp_src, smp_dst: the Samplers the
+    two frames were made with (one kind and size, no pixel lists), aov_src, aov_dst: rt.sample_aov's dicts for
+    them.  Returns what reproject returns."""
+    if (smp_src.width, smp_src.height) != (gbuf_src.width, gbuf_src.height):
+        raise ValueError("the source sampler's frame is not the G-buffer's")
+    return _reproject(gbuf_src, aov_src, smp_src, aov_dst, smp_dst, out, stats, options, True)
+
+
 def reproject(gbuf_src, aov_src, cam_src, aov_dst, cam_dst, out=None, stats=False, **options):
     """rt_reproject: carries gbuf_src (rendered at cam_src) over to cam_dst.  aov_src, aov_dst: the dicts
     rt.render_aov returns for the two cameras (numpy arrays, uploaded here) or dicts of integer device
     pointers; keys depth, normal and optionally triangle.  Fills `out` (its RNG states are left alone) or
     returns a new GBuffer whose RNG states are gbuf_src's, so the per-pixel streams continue; with stats=True
     returns (gbuf, dict of REPROJECT_STATS).  Options: reproject_options."""
+    return _reproject(gbuf_src, aov_src, cam_src, aov_dst, cam_dst, out, stats, options, False)
+
+
+def _reproject(gbuf_src, aov_src, cam_src, aov_dst, cam_dst, out, stats, options, samplers):
     W, H = gbuf_src.width, gbuf_src.height
     n = W * H
     L = lib()
@@ -1136,7 +1255,10 @@ def reproject(gbuf_src, aov_src, cam_src, aov_dst, cam_dst, out=None, stats=Fals
         if stats:
             check(L.rt_memset(d_st, 0, st.nbytes))
             options = dict(options, stats=d_st)
-        reproject_device(gbuf_src.g, sides[0], cam_src, sides[1], cam_dst, W, H, out.g, **options)
+        if samplers:
+            reproject_sampler_device(gbuf_src.g, sides[0], cam_src, sides[1], cam_dst, out.g, **options)
+        else:
+            reproject_device(gbuf_src.g, sides[0], cam_src, sides[1], cam_dst, W, H, out.g, **options)
         _synchronize_stream(options.get("stream"))
         if stats:
             check(L.rt_download(_ptr(st), d_st, st.nbytes))
@@ -1148,11 +1270,23 @@ def reproject_host(src_fb, src_sq, src_count, aov_src, cam_src, aov_dst, cam_dst
     src_sq and src_count (H, W); aov_src, aov_dst: dicts with depth (H, W), normal (H, W, 3) and optionally
     triangle (H, W); the frame size is taken from aov_dst's depth.  Returns (fb (H, W, 3) float32, sq (H, W)
     float32, count (H, W) int32), with stats=True also a dict of REPROJECT_STATS."""
+    return _reproject_host(src_fb, src_sq, src_count, aov_src, cam_src, aov_dst, cam_dst, stats, options, False)
+
+
+def reproject_sampler_host(src_fb, src_sq, src_count, aov_src, smp_src, aov_dst, smp_dst, stats=False, **options):
+    """rt_reproject_sampler_host: reproject_host with two Samplers in place of the two cameras (the arrays must have
+    their frame's size), bit-identical to reproject_sampler."""
+    return _reproject_host(src_fb, src_sq, src_count, aov_src, smp_src, aov_dst, smp_dst, stats, options, True)
+
+
+def _reproject_host(src_fb, src_sq, src_count, aov_src, cam_src, aov_dst, cam_dst, stats, options, samplers):
     depth = np.ascontiguousarray(aov_dst["depth"], dtype=np.float32)
     if depth.ndim != 2:
         raise ValueError("depth must have shape (H, W)")
     H, W = depth.shape
     n = W * H
+    if samplers and (cam_dst.width, cam_dst.height) != (W, H):
+        raise ValueError("the destination sampler's frame is not the arrays'")
 
     def arr(a, dtype, per):
         a = np.ascontiguousarray(a, dtype=dtype)
@@ -1175,6 +1309,13 @@ def reproject_host(src_fb, src_sq, src_count, aov_src, cam_src, aov_dst, cam_dst
     def opt_ptr(a):
         return None if a is None else _ptr(a)
     (s_d, s_n, s_t), (d_d, d_n, d_t) = sides
+    if samplers:
+        ss, sd = _frame_sampler_struct(cam_src), _frame_sampler_struct(cam_dst)
+        check(lib().rt_reproject_sampler_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(s_d), _ptr(s_n), opt_ptr(s_t),
+                                              ctypes.byref(ss), _ptr(d_d), _ptr(d_n), opt_ptr(d_t), ctypes.byref(sd),
+                                              _ptr(out_fb), _ptr(out_sq), _ptr(out_count), _ptr(st), ctypes.byref(o)))
+        out = (out_fb, out_sq, out_count)
+        return out + (dict(zip(REPROJECT_STATS, (int(v) for v in st))),) if stats else out
     check(lib().rt_reproject_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(s_d), _ptr(s_n), opt_ptr(s_t), cam_src,
                                   _ptr(d_d), _ptr(d_n), opt_ptr(d_t), cam_dst, W, H, _ptr(out_fb), _ptr(out_sq),
                                   _ptr(out_count), _ptr(st), ctypes.byref(o)))
