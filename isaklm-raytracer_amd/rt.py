@@ -6,6 +6,7 @@ The product path is the in-tree libisaklm_rt.so (HIP kernels for gfx950);
 importing this module fails loudly if it is missing — there is no CPU
 fallback.
 """
+import contextlib
 import ctypes
 import os
 
@@ -441,29 +442,21 @@ class GBuffer:
     def n(self):
         return self.width * self.height
 
+    ARRAYS = {"frame_buffer": (np.float32, (3,)), "squared_luminance": (np.float32, ()),
+              "sample_count": (np.int32, ()), "random_numbers": (np.uint32, ())}
+
+    def array(self, name):
+        """one of the G_Buffer's four arrays (ARRAYS) as a DeviceArray that does not own it"""
+        dtype, per = self.ARRAYS[name]
+        return DeviceArray.at(getattr(self.g, name), (self.n,) + per, dtype)
+
     def download(self):
-        n = self.n
-        fb = np.zeros((n, 3), dtype=np.float32)
-        sq = np.zeros(n, dtype=np.float32)
-        cnt = np.zeros(n, dtype=np.int32)
-        rng = np.zeros(n, dtype=np.uint32)
-        L = lib()
-        check(L.rt_download(_ptr(fb), self.g.frame_buffer, fb.nbytes))
-        check(L.rt_download(_ptr(sq), self.g.squared_luminance, sq.nbytes))
-        check(L.rt_download(_ptr(cnt), self.g.sample_count, cnt.nbytes))
-        check(L.rt_download(_ptr(rng), self.g.random_numbers, rng.nbytes))
-        return fb, sq, cnt, rng
+        """(fb (n, 3) float32, sq (n,) float32, cnt (n,) int32, rng (n,) uint32)"""
+        return tuple(self.array(name).read() for name in self.ARRAYS)
 
     def upload(self, fb, sq, cnt, rng):
-        L = lib()
-        fb = np.ascontiguousarray(fb, dtype=np.float32)
-        sq = np.ascontiguousarray(sq, dtype=np.float32)
-        cnt = np.ascontiguousarray(cnt, dtype=np.int32)
-        rng = np.ascontiguousarray(rng, dtype=np.uint32)
-        check(L.rt_upload(self.g.frame_buffer, _ptr(fb), fb.nbytes))
-        check(L.rt_upload(self.g.squared_luminance, _ptr(sq), sq.nbytes))
-        check(L.rt_upload(self.g.sample_count, _ptr(cnt), cnt.nbytes))
-        check(L.rt_upload(self.g.random_numbers, _ptr(rng), rng.nbytes))
+        for name, a in zip(self.ARRAYS, (fb, sq, cnt, rng)):
+            self.array(name).upload(a)
 
     def save(self, path, sample_count):
         """checkpoint (rt_gbuffer_save): the whole progressive state + the caller's sample count"""
@@ -545,32 +538,107 @@ def query_options(traversal=None, stream=None, stats=None):
     return o
 
 
-class _DeviceBytes:
-    """a device allocation of the C-ABI, freed on exit"""
+class DeviceArray:
+    """A device allocation of the C-ABI that knows the shape and dtype of the numpy array it holds.
+    DeviceArray(a) uploads a copy of the array `a`; DeviceArray(shape, dtype) is uninitialised, or zeroed with
+    zero=True.  `.p` is the c_void_p the *_device calls take; they, and any ctypes call, take the object itself too.
+    A context manager: freed on exit.  A zero-size array still owns an allocation; its copies are skipped."""
 
-    def __init__(self, nbytes):
+    def __init__(self, a, dtype=None, zero=False):
+        if dtype is None:
+            a = np.ascontiguousarray(a)
+            self._describe(a.shape, a.dtype)
+        else:
+            self._describe(a, dtype)
+        self.owned = True
         self.p = ctypes.c_void_p()
-        check(lib().rt_device_alloc(ctypes.byref(self.p), max(int(nbytes), 16)))
+        check(lib().rt_device_alloc(ctypes.byref(self.p), max(self.nbytes, 16)))
+        try:
+            if dtype is None:
+                self.upload(a)
+            elif zero:
+                self.zero()
+        except BaseException:
+            self.free()
+            raise
 
-    def __enter__(self):
+    @classmethod
+    def at(cls, p, shape, dtype):
+        """device memory someone else owns (a G_Buffer's array, a tensor's data_ptr()) as an array: free() leaves
+        it alone"""
+        self = cls.__new__(cls)
+        self._describe(shape, dtype)
+        self.owned, self.p = False, ctypes.c_void_p(_int_ptr(p))
+        return self
+
+    def _describe(self, shape, dtype):
+        self.shape = (int(shape),) if np.ndim(shape) == 0 else tuple(int(v) for v in shape)
+        self.dtype = np.dtype(dtype)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+
+    @property
+    def _as_parameter_(self):
         return self.p
 
+    def upload(self, a):
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        if a.nbytes != self.nbytes:
+            raise ValueError(f"an array of {a.nbytes} bytes does not fill a device array of {self.nbytes}")
+        if self.nbytes:
+            check(lib().rt_upload(self.p, _ptr(a), self.nbytes))
+
+    def read(self):
+        """a new numpy array of the device array's shape and dtype"""
+        out = np.empty(self.shape, self.dtype)
+        if self.nbytes:
+            check(lib().rt_download(_ptr(out), self.p, self.nbytes))
+        return out
+
+    def zero(self):
+        if self.nbytes:
+            check(lib().rt_memset(self.p, 0, self.nbytes))
+
+    def free(self):
+        if self.p and self.owned:
+            lib().rt_free(self.p)
+        self.p = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
     def __exit__(self, *exc):
-        lib().rt_free(self.p)
+        self.free()
         return False
 
 
 def _int_ptr(p):
+    if isinstance(p, DeviceArray):
+        p = p.p
     return p.value if isinstance(p, ctypes.c_void_p) else p
 
 
-def trace_rays_device(dscene, rays_ptr, n, hits_ptr, surface_ptr=None, traversal=None, stream=None, stats_ptr=None):
-    """rt_trace_rays on device memory: integer device pointers (a torch tensor's data_ptr()) to n x 6 float32
-    rays, n RtRayHit (RAY_HIT, 16 B) and optionally n RtRaySurface (RAY_SURFACE, 80 B); stream: an integer
-    hipStream_t (torch.cuda.current_stream().cuda_stream) — the call is then only enqueued."""
-    o = query_options(traversal, stream, _int_ptr(stats_ptr))
-    check(lib().rt_trace_rays(dscene.prepared, _int_ptr(rays_ptr), int(n), _int_ptr(hits_ptr), _int_ptr(surface_ptr),
-                              ctypes.byref(o)))
+class _Staged(contextlib.ExitStack):
+    """the device arrays of one numpy-level call, freed together when it ends"""
+
+    def put(self, a, dtype=None, zero=False):
+        return self.enter_context(DeviceArray(a, dtype, zero))
+
+    def put_arrays(self, values):
+        """uploads the numpy arrays among `values`; anything else is a device pointer already"""
+        return [self.put(a) if isinstance(a, np.ndarray) else a for a in values]
+
+    def stats(self, names, wanted=True):
+        """the zeroed block a call adds its counts to — None, for the call too, when they are not wanted"""
+        return self.put(len(names), np.uint64, zero=True) if wanted else None
+
+
+def _stats_dict(names, words):
+    return dict(zip(names, (int(v) for v in words)))
+
+
+def _stats_out(names, block):
+    """what a stats block (_Staged.stats) adds to a call's returned tuple"""
+    return () if block is None else (_stats_dict(names, block.read()),)
 
 
 def _synchronize_stream(stream):
@@ -580,35 +648,67 @@ def _synchronize_stream(stream):
         check(lib().rt_synchronize())
 
 
+def _rays_array(rays):
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must have shape (n, 6)")
+    return rays
+
+
+def _rng_array(rng, n):
+    rng = np.asarray(rng)
+    if rng.dtype != np.uint32 or rng.shape != (n,):
+        raise ValueError("rng must be a uint32 array of shape (n,)")
+    return np.ascontiguousarray(rng)
+
+
+def _sums_to_add(n, radiance, sq, count=None):
+    """checks the arrays of an earlier call that an accumulating call adds to (None: not given)"""
+    if radiance is None and sq is not None:
+        raise ValueError("sq without radiance: pass both arrays of the earlier call to accumulate")
+    if count is not None and radiance is None:
+        raise ValueError("count array without radiance: pass the arrays of the earlier call to accumulate")
+    for name, a, shape, dt in (("radiance", radiance, (n, 3), np.float32), ("sq", sq, (n,), np.float32),
+                               ("count", count, (n,), np.int32)):
+        if a is not None and (np.asarray(a).dtype != dt or np.asarray(a).shape != shape):
+            raise ValueError(f"{name} must be a {np.dtype(dt).name} array of shape {shape}")
+
+
+def _frame_array(a, dtype, size, what="buffer does not match the frame size"):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.size != size:
+        raise ValueError(what)
+    return a
+
+
+def _opt_ptr(a):
+    return None if a is None else _ptr(a)
+
+
+def trace_rays_device(dscene, rays_ptr, n, hits_ptr, surface_ptr=None, traversal=None, stream=None, stats_ptr=None):
+    """rt_trace_rays on device memory: device pointers (integers such as a torch tensor's data_ptr(), or
+    DeviceArrays) to n x 6 float32 rays, n RtRayHit (RAY_HIT, 16 B) and optionally n RtRaySurface (RAY_SURFACE,
+    80 B); stream: an integer hipStream_t (torch.cuda.current_stream().cuda_stream) — the call is then only
+    enqueued."""
+    o = query_options(traversal, stream, _int_ptr(stats_ptr))
+    check(lib().rt_trace_rays(dscene.prepared, _int_ptr(rays_ptr), int(n), _int_ptr(hits_ptr), _int_ptr(surface_ptr),
+                              ctypes.byref(o)))
+
+
 def trace_rays(dscene, rays, surface=False, traversal=None, stream=None, stats=False):
     """Closest hits of `rays` — a numpy (n, 6) float32 array (origin, direction; directions are used as given,
     not normalised) — bit-identical to the reference's trace_ray.  Returns the RAY_HIT record array
     (triangle -1: miss); with surface=True also the RAY_SURFACE records; with stats=True also a dict of the
     call's counts (QUERY_STATS)."""
-    rays = np.ascontiguousarray(rays, dtype=np.float32)
-    if rays.ndim != 2 or rays.shape[1] != 6:
-        raise ValueError("rays must have shape (n, 6)")
+    rays = _rays_array(rays)
     n = len(rays)
-    L = lib()
-    hits = np.zeros(n, dtype=RAY_HIT)
-    surf = np.zeros(n, dtype=RAY_SURFACE) if surface else None
-    st = np.zeros(3, dtype=np.uint64)
-    with _DeviceBytes(rays.nbytes) as d_rays, _DeviceBytes(hits.nbytes) as d_hits, \
-            _DeviceBytes(surf.nbytes if surface else 0) as d_surf, _DeviceBytes(st.nbytes) as d_st:
-        if n:
-            check(L.rt_upload(d_rays, _ptr(rays), rays.nbytes))
-        if stats:
-            check(L.rt_memset(d_st, 0, st.nbytes))
-        trace_rays_device(dscene, d_rays, n, d_hits, d_surf if surface else None, traversal, stream,
-                          d_st if stats else None)
+    with _Staged() as s:
+        d_rays, d_hits = s.put(rays), s.put(n, RAY_HIT)
+        d_surf = s.put(n, RAY_SURFACE) if surface else None
+        d_st = s.stats(QUERY_STATS, stats)
+        trace_rays_device(dscene, d_rays, n, d_hits, d_surf, traversal, stream, d_st)
         _synchronize_stream(stream)
-        if n:
-            check(L.rt_download(_ptr(hits), d_hits, hits.nbytes))
-            if surface:
-                check(L.rt_download(_ptr(surf), d_surf, surf.nbytes))
-        if stats:
-            check(L.rt_download(_ptr(st), d_st, st.nbytes))
-    out = (hits,) + ((surf,) if surface else ()) + ((dict(zip(QUERY_STATS, (int(v) for v in st))),) if stats else ())
+        out = (d_hits.read(),) + ((d_surf.read(),) if surface else ()) + _stats_out(QUERY_STATS, d_st)
     return out[0] if len(out) == 1 else out
 
 
@@ -616,9 +716,9 @@ OCCLUSION_STATS = ("rays", "occluded", "kd_rays")  # rt_occluded's stats_device 
 
 
 def occluded_device(dscene, rays_ptr, tmax_ptr, n, out_ptr, traversal=None, stream=None, stats_ptr=None):
-    """rt_occluded on device memory: integer device pointers (a torch tensor's data_ptr()) to n x 6 float32
-    rays, n float32 tmax (None: +inf for every ray) and n output bytes (any alignment); stream: an integer
-    hipStream_t (torch.cuda.current_stream().cuda_stream) — the call is then only enqueued."""
+    """rt_occluded on device memory: device pointers (as trace_rays_device's) to n x 6 float32 rays, n float32
+    tmax (None: +inf for every ray) and n output bytes (any alignment); stream: an integer hipStream_t
+    (torch.cuda.current_stream().cuda_stream) — the call is then only enqueued."""
     o = query_options(traversal, stream, _int_ptr(stats_ptr))
     check(lib().rt_occluded(dscene.prepared, _int_ptr(rays_ptr), _int_ptr(tmax_ptr), int(n), _int_ptr(out_ptr),
                             ctypes.byref(o)))
@@ -629,34 +729,21 @@ def occluded(dscene, rays, tmax=None, traversal=None, stream=None, stats=False):
     scalar or an (n,) array in units of the ray parameter; None: +inf): a uint8 array, 1 where the
     reference's trace_ray hits with a ray parameter s < tmax.  With stats=True also a dict of the call's
     counts (OCCLUSION_STATS)."""
-    rays = np.ascontiguousarray(rays, dtype=np.float32)
-    if rays.ndim != 2 or rays.shape[1] != 6:
-        raise ValueError("rays must have shape (n, 6)")
+    rays = _rays_array(rays)
     n = len(rays)
     if tmax is not None:
         tmax = np.asarray(tmax, dtype=np.float32)
         if tmax.ndim not in (0, 1) or (tmax.ndim == 1 and len(tmax) != n):
             raise ValueError("tmax must be a scalar or have shape (n,)")
-        tmax = np.ascontiguousarray(np.broadcast_to(tmax, (n,)))
-    L = lib()
-    out = np.zeros(n, dtype=np.uint8)
-    st = np.zeros(3, dtype=np.uint64)
-    with _DeviceBytes(rays.nbytes) as d_rays, _DeviceBytes(4 * n) as d_tmax, _DeviceBytes(n) as d_out, \
-            _DeviceBytes(st.nbytes) as d_st:
-        if n:
-            check(L.rt_upload(d_rays, _ptr(rays), rays.nbytes))
-            if tmax is not None:
-                check(L.rt_upload(d_tmax, _ptr(tmax), tmax.nbytes))
-        if stats:
-            check(L.rt_memset(d_st, 0, st.nbytes))
-        occluded_device(dscene, d_rays, d_tmax if tmax is not None else None, n, d_out, traversal, stream,
-                        d_st if stats else None)
+        tmax = np.broadcast_to(tmax, (n,))
+    with _Staged() as s:
+        d_rays, d_out = s.put(rays), s.put(n, np.uint8)
+        d_tmax = None if tmax is None else s.put(tmax)
+        d_st = s.stats(OCCLUSION_STATS, stats)
+        occluded_device(dscene, d_rays, d_tmax, n, d_out, traversal, stream, d_st)
         _synchronize_stream(stream)
-        if n:
-            check(L.rt_download(_ptr(out), d_out, out.nbytes))
-        if stats:
-            check(L.rt_download(_ptr(st), d_st, st.nbytes))
-    return (out, dict(zip(OCCLUSION_STATS, (int(v) for v in st)))) if stats else out
+        out = (d_out.read(),) + _stats_out(OCCLUSION_STATS, d_st)
+    return out if stats else out[0]
 
 
 PATH_STATS = ("rays", "paths", "trace_calls", "cut_paths", "max_depth")  # RtPathOptions.stats_device [0..4]
@@ -678,13 +765,21 @@ def path_options(samples=1, max_depth=0, accumulate=False, traversal=None, strea
 
 def trace_paths_device(dscene, rays_ptr, rng_ptr, n, radiance_ptr, sq_ptr=None, samples=1, max_depth=0,
                        accumulate=False, traversal=None, stream=None, stats_ptr=None):
-    """rt_trace_paths on device memory: integer device pointers (a torch tensor's data_ptr()) to n x 6 float32
-    rays, n uint32 RNG states (read and written), n x 3 float32 radiance sums and optionally n float32 sums of
-    squared luminance; stream: an integer hipStream_t (torch.cuda.current_stream().cuda_stream) — the call is
-    then only enqueued."""
+    """rt_trace_paths on device memory: device pointers (as trace_rays_device's) to n x 6 float32 rays, n uint32
+    RNG states (read and written), n x 3 float32 radiance sums and optionally n float32 sums of squared
+    luminance; stream: an integer hipStream_t (torch.cuda.current_stream().cuda_stream) — the call is then only
+    enqueued."""
     o = path_options(samples, max_depth, accumulate, traversal, stream, _int_ptr(stats_ptr))
     check(lib().rt_trace_paths(dscene.prepared, _int_ptr(rays_ptr), _int_ptr(rng_ptr), int(n), _int_ptr(radiance_ptr),
                                _int_ptr(sq_ptr), ctypes.byref(o)))
+
+
+def _put_sums(s, n, radiance, sq):
+    """the radiance and sq sums of a path call on the device: the caller's arrays to add to (an absent sq: zeros),
+    or uninitialised ones the call writes"""
+    if radiance is None:
+        return s.put((n, 3), np.float32), s.put(n, np.float32)
+    return s.put(radiance), s.put(sq) if sq is not None else s.put(n, np.float32, zero=True)
 
 
 def trace_paths(dscene, rays, rng, samples=1, max_depth=0, traversal=None, stream=None, stats=False, radiance=None,
@@ -694,45 +789,18 @@ def trace_paths(dscene, rays, rng, samples=1, max_depth=0, traversal=None, strea
     (n, 3) float32, sq (n,) float32, rng_out (n,) uint32): the SUMS of L and of luminance(L)^2 over the samples
     and the RNG states after them; with stats=True also a dict of the call's counts (PATH_STATS).  Passing
     `radiance` (and `sq`) arrays of an earlier call accumulates onto them (they are not modified)."""
-    rays = np.ascontiguousarray(rays, dtype=np.float32)
-    if rays.ndim != 2 or rays.shape[1] != 6:
-        raise ValueError("rays must have shape (n, 6)")
+    rays = _rays_array(rays)
     n = len(rays)
-    rng = np.asarray(rng)
-    if rng.dtype != np.uint32 or rng.shape != (n,):
-        raise ValueError("rng must be a uint32 array of shape (n,)")
-    if radiance is None and sq is not None:
-        raise ValueError("sq without radiance: pass both arrays of the earlier call to accumulate")
-    for name, a, shape in (("radiance", radiance, (n, 3)), ("sq", sq, (n,))):
-        if a is not None and (np.asarray(a).dtype != np.float32 or np.asarray(a).shape != shape):
-            raise ValueError(f"{name} must be a float32 array of shape {shape}")
-    accumulate = radiance is not None
-    rng = np.ascontiguousarray(rng).copy()
-    rad = np.ascontiguousarray(radiance).copy() if accumulate else np.zeros((n, 3), np.float32)
-    sqv = np.ascontiguousarray(sq).copy() if sq is not None else np.zeros(n, np.float32)
-    L = lib()
-    st = np.zeros(5, dtype=np.uint64)
-    with _DeviceBytes(rays.nbytes) as d_rays, _DeviceBytes(rng.nbytes) as d_rng, _DeviceBytes(rad.nbytes) as d_rad, \
-            _DeviceBytes(sqv.nbytes) as d_sq, _DeviceBytes(st.nbytes) as d_st:
-        if n:
-            check(L.rt_upload(d_rays, _ptr(rays), rays.nbytes))
-            check(L.rt_upload(d_rng, _ptr(rng), rng.nbytes))
-            if accumulate:
-                check(L.rt_upload(d_rad, _ptr(rad), rad.nbytes))
-                check(L.rt_upload(d_sq, _ptr(sqv), sqv.nbytes))
-        if stats:
-            check(L.rt_memset(d_st, 0, st.nbytes))
-        trace_paths_device(dscene, d_rays, d_rng, n, d_rad, d_sq, samples, max_depth, accumulate, traversal, stream,
-                           d_st if stats else None)
+    rng = _rng_array(rng, n)
+    _sums_to_add(n, radiance, sq)
+    with _Staged() as s:
+        d_rays, d_rng = s.put(rays), s.put(rng)
+        d_rad, d_sq = _put_sums(s, n, radiance, sq)
+        d_st = s.stats(PATH_STATS, stats)
+        trace_paths_device(dscene, d_rays, d_rng, n, d_rad, d_sq, samples, max_depth, radiance is not None, traversal,
+                           stream, d_st)
         _synchronize_stream(stream)
-        if n:
-            check(L.rt_download(_ptr(rad), d_rad, rad.nbytes))
-            check(L.rt_download(_ptr(sqv), d_sq, sqv.nbytes))
-            check(L.rt_download(_ptr(rng), d_rng, rng.nbytes))
-        if stats:
-            check(L.rt_download(_ptr(st), d_st, st.nbytes))
-    out = (rad, sqv, rng)
-    return out + (dict(zip(PATH_STATS, (int(v) for v in st))),) if stats else out
+        return (d_rad.read(), d_sq.read(), d_rng.read()) + _stats_out(PATH_STATS, d_st)
 
 
 # ---------------------------------------------------------------- path samplers
@@ -773,53 +841,32 @@ class Sampler:
                          _int_ptr(points_ptr))
 
 
+def _sampler_lists(sampler, put):
+    """(pixels, points) of a Sampler as a call takes them: `put` makes an array's pointer (an upload, or the host
+    array's own).  An empty list still is a list: the call sees the non-null dummies 4 and 8 (n == 0 is answered
+    before a pointer is looked at)."""
+    return [None if a is None else put(a) if a.size else dummy
+            for a, dummy in ((sampler.pixels, 4), (sampler.points, 8))]
+
+
 def sample_paths_device(dscene, sampler, rng_ptr, n, radiance_ptr, sq_ptr=None, count_ptr=None, samples=1, max_depth=0,
                         accumulate=False, traversal=None, stream=None, stats_ptr=None, pixels_ptr=None,
                         points_ptr=None, adaptive=None):
     """rt_sample_paths on device memory: `sampler` a Sampler (its arrays are not used: pixels_ptr / points_ptr
-    are the device pointers to them); integer device pointers to n uint32 RNG states (read and written), n x 3
-    float32 radiance sums, optionally n float32 sums of squared luminance and n int32 sample counts — a
-    G_Buffer's four arrays, for a whole frame; stream: an integer hipStream_t — the call is then only enqueued.
-    adaptive=(min_samples, tolerance): rt_sample_paths_adaptive — the renderer's adaptive test before every
-    sample (sq_ptr and count_ptr are then required)."""
+    are the device pointers to them); device pointers (as trace_rays_device's) to n uint32 RNG states (read and
+    written), n x 3 float32 radiance sums, optionally n float32 sums of squared luminance and n int32 sample
+    counts — a G_Buffer's four arrays, for a whole frame; stream: an integer hipStream_t — the call is then only
+    enqueued.  adaptive=(min_samples, tolerance): rt_sample_paths_adaptive — the renderer's adaptive test before
+    every sample (sq_ptr and count_ptr are then required)."""
     o = path_options(samples, max_depth, accumulate, traversal, stream, _int_ptr(stats_ptr))
     smp = sampler.struct(pixels_ptr, points_ptr)
-    if adaptive is not None:
+    args = (dscene.prepared, ctypes.byref(smp), _int_ptr(rng_ptr), int(n), _int_ptr(radiance_ptr), _int_ptr(sq_ptr),
+            _int_ptr(count_ptr), ctypes.byref(o))
+    if adaptive is None:
+        check(lib().rt_sample_paths(*args))
+    else:
         ad = RtAdaptive(int(adaptive[0]), float(adaptive[1]))
-        check(lib().rt_sample_paths_adaptive(dscene.prepared, ctypes.byref(smp), _int_ptr(rng_ptr), int(n),
-                                             _int_ptr(radiance_ptr), _int_ptr(sq_ptr), _int_ptr(count_ptr),
-                                             ctypes.byref(o), ctypes.byref(ad)))
-        return
-    check(lib().rt_sample_paths(dscene.prepared, ctypes.byref(smp), _int_ptr(rng_ptr), int(n), _int_ptr(radiance_ptr),
-                                _int_ptr(sq_ptr), _int_ptr(count_ptr), ctypes.byref(o)))
-
-
-class _SamplerArrays:
-    """a Sampler's pixel list and points on the device for the length of a call"""
-
-    def __init__(self, sampler):
-        self.sampler = sampler
-        self.arrays = [a if a is not None and a.nbytes else None for a in (sampler.pixels, sampler.points)]
-        self.ctx = [_DeviceBytes(a.nbytes) if a is not None else None for a in self.arrays]
-
-    def __enter__(self):
-        ptrs = []
-        for a, c in zip(self.arrays, self.ctx):
-            ptrs.append(c.__enter__() if c else None)
-            if c:
-                check(lib().rt_upload(ptrs[-1], _ptr(a), a.nbytes))
-        # (an empty list still is a list: n == 0 is answered before the pointer is looked at)
-        if self.sampler.pixels is not None and ptrs[0] is None:
-            ptrs[0] = 4
-        if self.sampler.points is not None and ptrs[1] is None:
-            ptrs[1] = 8
-        return ptrs
-
-    def __exit__(self, *exc):
-        for c in self.ctx:
-            if c:
-                c.__exit__(*exc)
-        return False
+        check(lib().rt_sample_paths_adaptive(*args, ctypes.byref(ad)))
 
 
 def sample_paths(dscene, sampler, rng, samples=1, max_depth=0, traversal=None, stream=None, stats=False,
@@ -837,50 +884,24 @@ def sample_paths(dscene, sampler, rng, samples=1, max_depth=0, traversal=None, s
         if count is None or count is False:
             count = True
     n = sampler.n
-    rng = np.asarray(rng)
-    if rng.dtype != np.uint32 or rng.shape != (n,):
-        raise ValueError("rng must be a uint32 array of shape (n,)")
-    if radiance is None and sq is not None:
-        raise ValueError("sq without radiance: pass both arrays of the earlier call to accumulate")
+    rng = _rng_array(rng, n)
     want_count = count is not None and count is not False
     count_arr = None if count is None or isinstance(count, bool) else np.asarray(count)
-    if count_arr is not None and radiance is None:
-        raise ValueError("count array without radiance: pass the arrays of the earlier call to accumulate")
-    for name, a, shape, dt in (("radiance", radiance, (n, 3), np.float32), ("sq", sq, (n,), np.float32),
-                               ("count", count_arr, (n,), np.int32)):
-        if a is not None and (np.asarray(a).dtype != dt or np.asarray(a).shape != shape):
-            raise ValueError(f"{name} must be a {np.dtype(dt).name} array of shape {shape}")
+    _sums_to_add(n, radiance, sq, count_arr)
     accumulate = radiance is not None
-    rng = np.ascontiguousarray(rng).copy()
-    rad = np.ascontiguousarray(radiance).copy() if accumulate else np.zeros((n, 3), np.float32)
-    sqv = np.ascontiguousarray(sq).copy() if sq is not None else np.zeros(n, np.float32)
-    cnt = np.ascontiguousarray(count_arr).copy() if count_arr is not None else np.zeros(n, np.int32)
-    L = lib()
-    st = np.zeros(5, dtype=np.uint64)
-    with _SamplerArrays(sampler) as (d_pix, d_pts), _DeviceBytes(rng.nbytes) as d_rng, \
-            _DeviceBytes(rad.nbytes) as d_rad, _DeviceBytes(sqv.nbytes) as d_sq, _DeviceBytes(cnt.nbytes) as d_cnt, \
-            _DeviceBytes(st.nbytes) as d_st:
-        if n:
-            check(L.rt_upload(d_rng, _ptr(rng), rng.nbytes))
-            if accumulate:
-                check(L.rt_upload(d_rad, _ptr(rad), rad.nbytes))
-                check(L.rt_upload(d_sq, _ptr(sqv), sqv.nbytes))
-                check(L.rt_upload(d_cnt, _ptr(cnt), cnt.nbytes))
-        if stats:
-            check(L.rt_memset(d_st, 0, st.nbytes))
-        sample_paths_device(dscene, sampler, d_rng, n, d_rad, d_sq, d_cnt if want_count else None, samples, max_depth,
-                            accumulate, traversal, stream, d_st if stats else None, d_pix, d_pts, adaptive)
+    with _Staged() as s:
+        d_pix, d_pts = _sampler_lists(sampler, s.put)
+        d_rng = s.put(rng)
+        d_rad, d_sq = _put_sums(s, n, radiance, sq)
+        d_cnt = None
+        if want_count:
+            d_cnt = s.put(count_arr) if count_arr is not None else s.put(n, np.int32, zero=accumulate)
+        d_st = s.stats(PATH_STATS, stats)
+        sample_paths_device(dscene, sampler, d_rng, n, d_rad, d_sq, d_cnt, samples, max_depth, accumulate, traversal,
+                            stream, d_st, d_pix, d_pts, adaptive)
         _synchronize_stream(stream)
-        if n:
-            check(L.rt_download(_ptr(rad), d_rad, rad.nbytes))
-            check(L.rt_download(_ptr(sqv), d_sq, sqv.nbytes))
-            check(L.rt_download(_ptr(rng), d_rng, rng.nbytes))
-            if want_count:
-                check(L.rt_download(_ptr(cnt), d_cnt, cnt.nbytes))
-        if stats:
-            check(L.rt_download(_ptr(st), d_st, st.nbytes))
-    out = (rad, sqv, rng) + ((cnt,) if want_count else ())
-    return out + (dict(zip(PATH_STATS, (int(v) for v in st))),) if stats else out
+        return (d_rad.read(), d_sq.read(), d_rng.read()) + ((d_cnt.read(),) if want_count else ()) + \
+            _stats_out(PATH_STATS, d_st)
 
 
 CONVERGENCE_STATS = ("elements", "open", "below_min", "samples")  # rt_convergence's stats [0..3]
@@ -888,9 +909,9 @@ CONVERGENCE_STATS = ("elements", "open", "below_min", "samples")  # rt_convergen
 
 def convergence_device(radiance_ptr, sq_ptr, count_ptr, n, min_samples, tolerance, rel_error_ptr=None, stats_ptr=None,
                        stream=None):
-    """rt_convergence on device memory: integer device pointers to n x 3 float32 radiance sums, n float32 sums of
-    squared luminance and n int32 sample counts (a G_Buffer's arrays, or sample_paths' outputs); optionally n
-    float32 for the relative-error map and 4 u64 the call adds CONVERGENCE_STATS to."""
+    """rt_convergence on device memory: device pointers (as trace_rays_device's) to n x 3 float32 radiance sums,
+    n float32 sums of squared luminance and n int32 sample counts (a G_Buffer's arrays, or sample_paths'
+    outputs); optionally n float32 for the relative-error map and 4 u64 the call adds CONVERGENCE_STATS to."""
     check(lib().rt_convergence(_int_ptr(radiance_ptr), _int_ptr(sq_ptr), _int_ptr(count_ptr), int(n), int(min_samples),
                                float(tolerance), _int_ptr(rel_error_ptr), _int_ptr(stats_ptr), stream))
 
@@ -910,22 +931,12 @@ def convergence(radiance, sq, count, min_samples, tolerance, rel_error=False):
     of elements the adaptive test would sample on the next pass, 0 = converged; with rel_error=True also the (n,)
     float32 relative-error map."""
     radiance, sq, count, n = _convergence_arrays(radiance, sq, count)
-    L = lib()
-    st = np.zeros(4, dtype=np.uint64)
-    err = np.zeros(n, dtype=np.float32)
-    with _DeviceBytes(radiance.nbytes) as d_rad, _DeviceBytes(sq.nbytes) as d_sq, _DeviceBytes(count.nbytes) as d_cnt, \
-            _DeviceBytes(err.nbytes) as d_err, _DeviceBytes(st.nbytes) as d_st:
-        if n:
-            check(L.rt_upload(d_rad, _ptr(radiance), radiance.nbytes))
-            check(L.rt_upload(d_sq, _ptr(sq), sq.nbytes))
-            check(L.rt_upload(d_cnt, _ptr(count), count.nbytes))
-        check(L.rt_memset(d_st, 0, st.nbytes))
-        convergence_device(d_rad, d_sq, d_cnt, n, min_samples, tolerance, d_err if rel_error and n else None, d_st)
-        check(L.rt_download(_ptr(st), d_st, st.nbytes))
-        if rel_error and n:
-            check(L.rt_download(_ptr(err), d_err, err.nbytes))
-    stats = dict(zip(CONVERGENCE_STATS, (int(v) for v in st)))
-    return (stats, err) if rel_error else stats
+    with _Staged() as s:
+        d_err = s.put(n, np.float32) if rel_error and n else None
+        d_st = s.stats(CONVERGENCE_STATS)
+        convergence_device(s.put(radiance), s.put(sq), s.put(count), n, min_samples, tolerance, d_err, d_st)
+        stats = _stats_dict(CONVERGENCE_STATS, d_st.read())
+        return (stats, d_err.read() if d_err is not None else np.zeros(0, np.float32)) if rel_error else stats
 
 
 def convergence_host(radiance, sq, count, min_samples, tolerance, rel_error=False):
@@ -935,46 +946,30 @@ def convergence_host(radiance, sq, count, min_samples, tolerance, rel_error=Fals
     err = np.zeros(max(n, 1), dtype=np.float32)
     check(lib().rt_convergence_host(_ptr(radiance), _ptr(sq), _ptr(count), n, int(min_samples), float(tolerance),
                                     _ptr(err) if rel_error else None, _ptr(st)))
-    stats = dict(zip(CONVERGENCE_STATS, (int(v) for v in st)))
+    stats = _stats_dict(CONVERGENCE_STATS, st)
     return (stats, err[:n]) if rel_error else stats
-
-
-def _sampler_rng(sampler, rng):
-    n = sampler.n
-    if rng is None:
-        return n, None
-    rng = np.asarray(rng)
-    if rng.dtype != np.uint32 or rng.shape != (n,):
-        raise ValueError("rng must be a uint32 array of shape (n,)")
-    return n, np.ascontiguousarray(rng).copy()
 
 
 def sampler_rays(sampler, rng=None):
     """rt_sampler_rays: one sample's rays of every element of `sampler`, drawn on the device from the (n,) uint32
     RNG states `rng`: (rays (n, 6) float32, rng_out).  rng None: the centre rays (image kinds), rays alone."""
-    n, rng = _sampler_rng(sampler, rng)
-    rays = np.zeros((n, 6), dtype=np.float32)
-    L = lib()
-    with _SamplerArrays(sampler) as (d_pix, d_pts), _DeviceBytes(4 * n) as d_rng, _DeviceBytes(rays.nbytes) as d_rays:
-        if n and rng is not None:
-            check(L.rt_upload(d_rng, _ptr(rng), rng.nbytes))
-        smp = sampler.struct(d_pix, d_pts)
-        check(L.rt_sampler_rays(ctypes.byref(smp), d_rng if rng is not None else None, n, d_rays, None))
-        if n:
-            check(L.rt_download(_ptr(rays), d_rays, rays.nbytes))
-            if rng is not None:
-                check(L.rt_download(_ptr(rng), d_rng, rng.nbytes))
-    return rays if rng is None else (rays, rng)
+    n = sampler.n
+    rng = None if rng is None else _rng_array(rng, n)
+    with _Staged() as s:
+        smp = sampler.struct(*_sampler_lists(sampler, s.put))
+        d_rng = None if rng is None else s.put(rng)
+        d_rays = s.put((n, 6), np.float32)
+        check(lib().rt_sampler_rays(ctypes.byref(smp), d_rng, n, d_rays, None))
+        return d_rays.read() if rng is None else (d_rays.read(), d_rng.read())
 
 
 def sampler_rays_host(sampler, rng=None):
     """rt_sampler_rays_host: sampler_rays computed on the host, bit for bit (no GPU is touched)."""
-    n, rng = _sampler_rng(sampler, rng)
+    n = sampler.n
+    rng = None if rng is None else _rng_array(rng, n).copy()
     rays = np.zeros((max(n, 1), 6), dtype=np.float32)
-    pix, pts = sampler.pixels, sampler.points
-    smp = sampler.struct(None if pix is None else (pix.ctypes.data if len(pix) else 4),
-                         None if pts is None else (pts.ctypes.data if len(pts) else 8))
-    check(lib().rt_sampler_rays_host(ctypes.byref(smp), _ptr(rng) if rng is not None else None, n, _ptr(rays)))
+    smp = sampler.struct(*_sampler_lists(sampler, _ptr))
+    check(lib().rt_sampler_rays_host(ctypes.byref(smp), _opt_ptr(rng), n, _ptr(rays)))
     rays = rays[:n]
     return rays if rng is None else (rays, rng)
 
@@ -982,35 +977,47 @@ def sampler_rays_host(sampler, rng=None):
 def camera_rays(camera, width, height):
     """rt_camera_rays: the (width*height, 6) float32 pixel-centre rays of `camera` (ray y*width + x, row 0 =
     bottom): the renderer's camera ray with both jitter draws 0.5 and no aperture offset."""
-    rays = np.zeros((width * height, 6), dtype=np.float32)
-    with _DeviceBytes(rays.nbytes) as d:
+    with DeviceArray((width * height, 6), np.float32) as d:
         check(lib().rt_camera_rays(camera, width, height, d, None))
-        check(lib().rt_download(_ptr(rays), d, rays.nbytes))
-    return rays
+        return d.read()
+
+
+# the first-hit feature buffers (RtAovBuffers' order): name -> (dtype, values per pixel)
+_AOVS = {"depth": (np.float32, 1), "normal": (np.float32, 3), "albedo": (np.float32, 3), "triangle": (np.int32, 1)}
+
+
+def _aov_buffers(depth, normal, albedo, triangle):
+    return RtAovBuffers(_int_ptr(depth), _int_ptr(normal), _int_ptr(albedo), _int_ptr(triangle))
+
+
+def _put_aov_outputs(s, lead):
+    """the four AOV arrays of a frame or pixel list of shape `lead` on the device: {name: DeviceArray}"""
+    return {k: s.put(lead + ((per,) if per > 1 else ()), dtype) for k, (dtype, per) in _AOVS.items()}
+
+
+def _aov_inputs(aov, names, W, H):
+    """aov's entries for `names` as a device call takes them: a numpy array, checked against the frame, is to be
+    uploaded for the call (_Staged.put_arrays); anything else is a device pointer already (None: no such buffer)"""
+    return [_frame_array(aov[k], _AOVS[k][0], W * H * _AOVS[k][1], f"aov[{k!r}] does not match the {W} x {H} frame")
+            if isinstance(aov.get(k), np.ndarray) else aov.get(k) for k in names]
 
 
 def render_aov(dscene, camera, width, height, traversal=None):
     """rt_render_aov: the first-hit feature buffers of the pixel-centre rays, as a dict of numpy arrays with
     row 0 = bottom: depth (H, W) float32 (inf: miss), normal and albedo (H, W, 3) float32, triangle (H, W)
     int32 (-1: miss)."""
-    n = width * height
-    out = {"depth": np.zeros((height, width), np.float32), "normal": np.zeros((height, width, 3), np.float32),
-           "albedo": np.zeros((height, width, 3), np.float32), "triangle": np.zeros((height, width), np.int32)}
-    L = lib()
-    with _DeviceBytes(n * 4) as d_depth, _DeviceBytes(n * 12) as d_normal, _DeviceBytes(n * 12) as d_albedo, \
-            _DeviceBytes(n * 4) as d_tri:
-        b = RtAovBuffers(d_depth, d_normal, d_albedo, d_tri)
+    with _Staged() as s:
+        d = _put_aov_outputs(s, (height, width))
+        b = _aov_buffers(*d.values())
         o = query_options(traversal)
-        check(L.rt_render_aov(dscene.prepared, camera, width, height, ctypes.byref(b), ctypes.byref(o)))
-        for name, d in (("depth", d_depth), ("normal", d_normal), ("albedo", d_albedo), ("triangle", d_tri)):
-            check(L.rt_download(_ptr(out[name]), d, out[name].nbytes))
-    return out
+        check(lib().rt_render_aov(dscene.prepared, camera, width, height, ctypes.byref(b), ctypes.byref(o)))
+        return {k: a.read() for k, a in d.items()}
 
 
 def sample_aov_device(dscene, sampler, n, aov_ptrs, traversal=None, stream=None, stats_ptr=None, pixels_ptr=None):
     """rt_sample_aov on device memory: `sampler` a Sampler (its pixel array is not used: pixels_ptr is the device
-    pointer to it), aov_ptrs (depth, normal, albedo, triangle) integer device pointers, any of them None."""
-    b = RtAovBuffers(*[_int_ptr(p) for p in aov_ptrs])
+    pointer to it), aov_ptrs (depth, normal, albedo, triangle) device pointers, any of them None."""
+    b = _aov_buffers(*aov_ptrs)
     o = query_options(traversal, stream, _int_ptr(stats_ptr))
     smp = sampler.struct(pixels_ptr, None)
     check(lib().rt_sample_aov(dscene.prepared, ctypes.byref(smp), int(n), ctypes.byref(b), ctypes.byref(o)))
@@ -1021,29 +1028,30 @@ def sample_aov(dscene, sampler, traversal=None, stats=False):
     (H, W, ...) with row 0 = bottom for a whole frame, (n, ...) for a pixel list (out-of-frame entries miss: depth
     inf, triangle -1); with stats=True also a dict of the call's counts (QUERY_STATS)."""
     n = sampler.n
-    lead = (sampler.height, sampler.width) if sampler.pixels is None else (n,)
-    out = {"depth": np.zeros(lead, np.float32), "normal": np.zeros(lead + (3,), np.float32),
-           "albedo": np.zeros(lead + (3,), np.float32), "triangle": np.zeros(lead, np.int32)}
-    L = lib()
-    st = np.zeros(3, dtype=np.uint64)
-    with _SamplerArrays(sampler) as (d_pix, _), _DeviceBytes(n * 4) as d_depth, _DeviceBytes(n * 12) as d_normal, \
-            _DeviceBytes(n * 12) as d_albedo, _DeviceBytes(n * 4) as d_tri, _DeviceBytes(st.nbytes) as d_st:
-        if stats:
-            check(L.rt_memset(d_st, 0, st.nbytes))
-        sample_aov_device(dscene, sampler, n, (d_depth, d_normal, d_albedo, d_tri), traversal, None,
-                          d_st if stats else None, d_pix)
-        if n:
-            for name, d in (("depth", d_depth), ("normal", d_normal), ("albedo", d_albedo), ("triangle", d_tri)):
-                check(L.rt_download(_ptr(out[name]), d, out[name].nbytes))
-        if stats:
-            check(L.rt_download(_ptr(st), d_st, st.nbytes))
-    return (out, dict(zip(QUERY_STATS, (int(v) for v in st)))) if stats else out
+    with _Staged() as s:
+        d_pix, _ = _sampler_lists(sampler, s.put)
+        d = _put_aov_outputs(s, (sampler.height, sampler.width) if sampler.pixels is None else (n,))
+        d_st = s.stats(QUERY_STATS, stats)
+        sample_aov_device(dscene, sampler, n, list(d.values()), traversal, None, d_st, d_pix)
+        out = ({k: a.read() for k, a in d.items()},) + _stats_out(QUERY_STATS, d_st)
+    return out if stats else out[0]
 
 
 def _frame_sampler_struct(sampler):
     """the RtSampler of a whole-frame call: a pixel list stays visible to the library (which refuses it) without
     being uploaded"""
     return sampler.struct(None if sampler.pixels is None else 4, None if sampler.points is None else 8)
+
+
+def _frame_entry(call, host, samplers, views, size):
+    """(entry point, view arguments, size arguments) of a frame call and its host twin (host "_host"): `call` takes
+    its views (Cameras; a None is no view) as they are and the frame's size; for whole-frame Samplers
+    `call`_sampler takes pointers to their RtSamplers and no size.  Resolves rt_denoise, rt_denoise_host,
+    rt_denoise_sampler, rt_denoise_sampler_host, rt_reproject, rt_reproject_host, rt_reproject_sampler and
+    rt_reproject_sampler_host."""
+    if not samplers:
+        return getattr(lib(), call + host), [v for v in views if v is not None], list(size)
+    return getattr(lib(), call + "_sampler" + host), [ctypes.byref(_frame_sampler_struct(v)) for v in views], []
 
 
 # ---------------------------------------------------------------- denoising
@@ -1057,27 +1065,30 @@ def denoise_options(iterations=0, sigma_lum=0.0, sigma_depth=0.0, normal_log2=0,
     return o
 
 
-def denoise_device(g, aov_ptrs, width, height, out_ptr, **options):
-    """rt_denoise on device memory: g a G_Buffer struct, aov_ptrs (depth, normal, albedo) integer device
-    pointers (albedo may be None with demodulate=False), out_ptr width*height*3 floats."""
-    b = RtAovBuffers(_int_ptr(aov_ptrs[0]), _int_ptr(aov_ptrs[1]), _int_ptr(aov_ptrs[2]), None)
+def _denoise_device(g, aov_ptrs, sampler, width, height, out_ptr, options):
+    """rt_denoise_sampler for a Sampler's frame, rt_denoise (sampler None) for a width x height one"""
+    b = _aov_buffers(aov_ptrs[0], aov_ptrs[1], aov_ptrs[2], None)
     o = denoise_options(**options)
-    check(lib().rt_denoise(g, ctypes.byref(b), width, height, _int_ptr(out_ptr), ctypes.byref(o)))
+    fn, view, size = _frame_entry("rt_denoise", "", sampler is not None, [sampler], (width, height))
+    check(fn(g, ctypes.byref(b), *view, *size, _int_ptr(out_ptr), ctypes.byref(o)))
+
+
+def denoise_device(g, aov_ptrs, width, height, out_ptr, **options):
+    """rt_denoise on device memory: g a G_Buffer struct, aov_ptrs (depth, normal, albedo) device pointers
+    (integers or DeviceArrays; albedo may be None with demodulate=False), out_ptr width*height*3 floats."""
+    _denoise_device(g, aov_ptrs, None, width, height, out_ptr, options)
 
 
 def denoise_sampler_device(g, aov_ptrs, sampler, out_ptr, **options):
     """rt_denoise_sampler on device memory: denoise_device with a Sampler (a whole frame of an image kind) in place
     of width and height; an equirect sampler's x axis is periodic."""
-    b = RtAovBuffers(_int_ptr(aov_ptrs[0]), _int_ptr(aov_ptrs[1]), _int_ptr(aov_ptrs[2]), None)
-    o = denoise_options(**options)
-    smp = _frame_sampler_struct(sampler)
-    check(lib().rt_denoise_sampler(g, ctypes.byref(b), ctypes.byref(smp), _int_ptr(out_ptr), ctypes.byref(o)))
+    _denoise_device(g, aov_ptrs, sampler, 0, 0, out_ptr, options)
 
 
 def denoise(gbuf, aov, **options):
     """rt_denoise: the denoised mean radiance of `gbuf` as (H, W, 3) float32, row 0 = bottom.  aov: the dict
-    rt.render_aov returns (numpy arrays, uploaded here) or a dict of integer device pointers; keys depth,
-    normal and — unless demodulate=False — albedo.  Options: denoise_options."""
+    rt.render_aov returns (numpy arrays, uploaded here) or a dict of device pointers; keys depth, normal and —
+    unless demodulate=False — albedo.  Options: denoise_options."""
     return _denoise(gbuf, aov, None, options)
 
 
@@ -1092,30 +1103,12 @@ def denoise_sampler(gbuf, aov, sampler, **options):
 
 def _denoise(gbuf, aov, sampler, options):
     W, H = gbuf.width, gbuf.height
-    n = W * H
-    L = lib()
-    out = np.zeros((H, W, 3), np.float32)
-    names = ("depth", "normal", "albedo")
-    host = {k: np.ascontiguousarray(aov[k], dtype=np.float32) for k in names
-            if aov.get(k) is not None and isinstance(aov[k], np.ndarray)}
-    with _DeviceBytes(n * 4) as d_depth, _DeviceBytes(n * 12) as d_normal, _DeviceBytes(n * 12) as d_albedo, \
-            _DeviceBytes(n * 12) as d_out:
-        ptrs = []
-        for k, d in zip(names, (d_depth, d_normal, d_albedo)):
-            if k in host:
-                if host[k].size != n * (1 if k == "depth" else 3):
-                    raise ValueError(f"aov[{k!r}] does not match the {W} x {H} frame")
-                check(L.rt_upload(d, _ptr(host[k]), host[k].nbytes))
-                ptrs.append(d)
-            else:
-                ptrs.append(aov.get(k))
-        if sampler is None:
-            denoise_device(gbuf.g, ptrs, W, H, d_out, **options)
-        else:
-            denoise_sampler_device(gbuf.g, ptrs, sampler, d_out, **options)
+    guides = _aov_inputs(aov, ("depth", "normal", "albedo"), W, H)
+    with _Staged() as s:
+        d_out = s.put((H, W, 3), np.float32)
+        _denoise_device(gbuf.g, s.put_arrays(guides), sampler, W, H, d_out, options)
         _synchronize_stream(options.get("stream"))
-        check(L.rt_download(_ptr(out), d_out, out.nbytes))
-    return out
+        return d_out.read()
 
 
 def denoise_host(fb, sq, count, depth, normal, albedo, **options):
@@ -1131,33 +1124,27 @@ def denoise_sampler_host(fb, sq, count, depth, normal, albedo, sampler, **option
     return _denoise_host(fb, sq, count, depth, normal, albedo, sampler, options)
 
 
-def _denoise_host(fb, sq, count, depth, normal, albedo, sampler, options):
+def _host_frame(depth, sampler, what):
+    """(depth as a float32 array, W, H) of a host twin's frame, which is `sampler`'s if one is given"""
     depth = np.ascontiguousarray(depth, dtype=np.float32)
     if depth.ndim != 2:
         raise ValueError("depth must have shape (H, W)")
     H, W = depth.shape
     if sampler is not None and (sampler.width, sampler.height) != (W, H):
-        raise ValueError("the sampler's frame is not the arrays'")
-    n = W * H
+        raise ValueError(what)
+    return depth, W, H
 
-    def arr(a, dtype, per):
-        a = np.ascontiguousarray(a, dtype=dtype)
-        if a.size != n * per:
-            raise ValueError("buffer does not match the frame size")
-        return a
-    fb, sq, count = arr(fb, np.float32, 3), arr(sq, np.float32, 1), arr(count, np.int32, 1)
-    normal = arr(normal, np.float32, 3)
-    albedo = None if albedo is None else arr(albedo, np.float32, 3)
+
+def _denoise_host(fb, sq, count, depth, normal, albedo, sampler, options):
+    depth, W, H = _host_frame(depth, sampler, "the sampler's frame is not the arrays'")
+    n = W * H
+    arrays = [_frame_array(fb, np.float32, 3 * n), _frame_array(sq, np.float32, n), _frame_array(count, np.int32, n),
+              depth, _frame_array(normal, np.float32, 3 * n),
+              None if albedo is None else _frame_array(albedo, np.float32, 3 * n)]
     out = np.zeros((H, W, 3), np.float32)
     o = denoise_options(**options)
-    if sampler is None:
-        check(lib().rt_denoise_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(depth), _ptr(normal),
-                                    None if albedo is None else _ptr(albedo), W, H, _ptr(out), ctypes.byref(o)))
-    else:
-        smp = _frame_sampler_struct(sampler)
-        check(lib().rt_denoise_sampler_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(depth), _ptr(normal),
-                                            None if albedo is None else _ptr(albedo), ctypes.byref(smp), _ptr(out),
-                                            ctypes.byref(o)))
+    fn, view, size = _frame_entry("rt_denoise", "_host", sampler is not None, [sampler], (W, H))
+    check(fn(*[_opt_ptr(a) for a in arrays], *view, *size, _ptr(out), ctypes.byref(o)))
     return out
 
 
@@ -1177,32 +1164,26 @@ def reproject_options(max_history=0, depth_tol=0.0, normal_min=0.0, match_triang
     return o
 
 
-def reproject_device(g_src, aov_src_ptrs, cam_src, aov_dst_ptrs, cam_dst, width, height, g_dst, **options):
-    """rt_reproject on device memory: g_src, g_dst G_Buffer structs, aov_*_ptrs (depth, normal, triangle)
-    integer device pointers (triangle may be None)."""
-    bs = RtAovBuffers(_int_ptr(aov_src_ptrs[0]), _int_ptr(aov_src_ptrs[1]), None, _int_ptr(aov_src_ptrs[2]))
-    bd = RtAovBuffers(_int_ptr(aov_dst_ptrs[0]), _int_ptr(aov_dst_ptrs[1]), None, _int_ptr(aov_dst_ptrs[2]))
+def _reproject_device(g_src, aov_src_ptrs, view_src, aov_dst_ptrs, view_dst, size, g_dst, options):
+    """rt_reproject for two Cameras and a (width, height) size, rt_reproject_sampler (size None) for two Samplers"""
+    bs, bd = (_aov_buffers(p[0], p[1], None, p[2]) for p in (aov_src_ptrs, aov_dst_ptrs))
     if "stats" in options:
         options = dict(options, stats=_int_ptr(options["stats"]))
     o = reproject_options(**options)
-    check(lib().rt_reproject(g_src, ctypes.byref(bs), cam_src, ctypes.byref(bd), cam_dst, width, height, g_dst,
-                             ctypes.byref(o)))
+    fn, (src, dst), size = _frame_entry("rt_reproject", "", size is None, (view_src, view_dst), size or ())
+    check(fn(g_src, ctypes.byref(bs), src, ctypes.byref(bd), dst, *size, g_dst, ctypes.byref(o)))
 
 
-_RP_AOVS = (("depth", np.float32, 1), ("normal", np.float32, 3), ("triangle", np.int32, 1))
+def reproject_device(g_src, aov_src_ptrs, cam_src, aov_dst_ptrs, cam_dst, width, height, g_dst, **options):
+    """rt_reproject on device memory: g_src, g_dst G_Buffer structs, aov_*_ptrs (depth, normal, triangle)
+    device pointers (integers or DeviceArrays; triangle may be None)."""
+    _reproject_device(g_src, aov_src_ptrs, cam_src, aov_dst_ptrs, cam_dst, (width, height), g_dst, options)
 
 
 def reproject_sampler_device(g_src, aov_src_ptrs, smp_src, aov_dst_ptrs, smp_dst, g_dst, **options):
     """rt_reproject_sampler on device memory: reproject_device with two Samplers (whole frames of one image kind
     and size) in place of the two cameras and the frame size."""
-    bs = RtAovBuffers(_int_ptr(aov_src_ptrs[0]), _int_ptr(aov_src_ptrs[1]), None, _int_ptr(aov_src_ptrs[2]))
-    bd = RtAovBuffers(_int_ptr(aov_dst_ptrs[0]), _int_ptr(aov_dst_ptrs[1]), None, _int_ptr(aov_dst_ptrs[2]))
-    if "stats" in options:
-        options = dict(options, stats=_int_ptr(options["stats"]))
-    o = reproject_options(**options)
-    ss, sd = _frame_sampler_struct(smp_src), _frame_sampler_struct(smp_dst)
-    check(lib().rt_reproject_sampler(g_src, ctypes.byref(bs), ctypes.byref(ss), ctypes.byref(bd), ctypes.byref(sd), g_dst,
-                                     ctypes.byref(o)))
+    _reproject_device(g_src, aov_src_ptrs, smp_src, aov_dst_ptrs, smp_dst, None, g_dst, options)
 
 
 def reproject_sampler(gbuf_src, aov_src, smp_src, aov_dst, smp_dst, out=None, stats=False, **options):
@@ -1216,53 +1197,29 @@ def reproject_sampler(gbuf_src, aov_src, smp_src, aov_dst, smp_dst, out=None, st
 
 def reproject(gbuf_src, aov_src, cam_src, aov_dst, cam_dst, out=None, stats=False, **options):
     """rt_reproject: carries gbuf_src (rendered at cam_src) over to cam_dst.  aov_src, aov_dst: the dicts
-    rt.render_aov returns for the two cameras (numpy arrays, uploaded here) or dicts of integer device
-    pointers; keys depth, normal and optionally triangle.  Fills `out` (its RNG states are left alone) or
-    returns a new GBuffer whose RNG states are gbuf_src's, so the per-pixel streams continue; with stats=True
-    returns (gbuf, dict of REPROJECT_STATS).  Options: reproject_options."""
+    rt.render_aov returns for the two cameras (numpy arrays, uploaded here) or dicts of device pointers; keys
+    depth, normal and optionally triangle.  Fills `out` (its RNG states are left alone) or returns a new
+    GBuffer whose RNG states are gbuf_src's, so the per-pixel streams continue; with stats=True returns (gbuf,
+    dict of REPROJECT_STATS).  Options: reproject_options."""
     return _reproject(gbuf_src, aov_src, cam_src, aov_dst, cam_dst, out, stats, options, False)
 
 
-def _reproject(gbuf_src, aov_src, cam_src, aov_dst, cam_dst, out, stats, options, samplers):
+def _reproject(gbuf_src, aov_src, view_src, aov_dst, view_dst, out, stats, options, samplers):
     W, H = gbuf_src.width, gbuf_src.height
-    n = W * H
-    L = lib()
+    if out is not None and (out.width, out.height) != (W, H):
+        raise ValueError("out does not match the source frame's size")
+    sides = [_aov_inputs(aov, ("depth", "normal", "triangle"), W, H) for aov in (aov_src, aov_dst)]
     if out is None:
         out = GBuffer(W, H)
-        rng = np.zeros(n, dtype=np.uint32)
-        check(L.rt_download(_ptr(rng), gbuf_src.g.random_numbers, rng.nbytes))
-        check(L.rt_upload(out.g.random_numbers, _ptr(rng), rng.nbytes))
-    elif (out.width, out.height) != (W, H):
-        raise ValueError("out does not match the source frame's size")
-    st = np.zeros(3, dtype=np.uint64)
-    with _DeviceBytes(n * 4) as sd, _DeviceBytes(n * 12) as sn, _DeviceBytes(n * 4) as stri, \
-            _DeviceBytes(n * 4) as dd, _DeviceBytes(n * 12) as dn, _DeviceBytes(n * 4) as dtri, \
-            _DeviceBytes(st.nbytes) as d_st:
-        sides = []
-        for aov, bufs in ((aov_src, (sd, sn, stri)), (aov_dst, (dd, dn, dtri))):
-            ptrs = []
-            for (k, dtype, per), d in zip(_RP_AOVS, bufs):
-                a = aov.get(k)
-                if isinstance(a, np.ndarray):
-                    a = np.ascontiguousarray(a, dtype=dtype)
-                    if a.size != n * per:
-                        raise ValueError(f"aov[{k!r}] does not match the {W} x {H} frame")
-                    check(L.rt_upload(d, _ptr(a), a.nbytes))
-                    ptrs.append(d)
-                else:
-                    ptrs.append(a)
-            sides.append(ptrs)
+        out.array("random_numbers").upload(gbuf_src.array("random_numbers").read())
+    with _Staged() as s:
+        d_st = s.stats(REPROJECT_STATS, stats)
         if stats:
-            check(L.rt_memset(d_st, 0, st.nbytes))
             options = dict(options, stats=d_st)
-        if samplers:
-            reproject_sampler_device(gbuf_src.g, sides[0], cam_src, sides[1], cam_dst, out.g, **options)
-        else:
-            reproject_device(gbuf_src.g, sides[0], cam_src, sides[1], cam_dst, W, H, out.g, **options)
+        _reproject_device(gbuf_src.g, s.put_arrays(sides[0]), view_src, s.put_arrays(sides[1]), view_dst,
+                          None if samplers else (W, H), out.g, options)
         _synchronize_stream(options.get("stream"))
-        if stats:
-            check(L.rt_download(_ptr(st), d_st, st.nbytes))
-    return (out, dict(zip(REPROJECT_STATS, (int(v) for v in st)))) if stats else out
+        return (out,) + _stats_out(REPROJECT_STATS, d_st) if stats else out
 
 
 def reproject_host(src_fb, src_sq, src_count, aov_src, cam_src, aov_dst, cam_dst, stats=False, **options):
@@ -1279,48 +1236,24 @@ def reproject_sampler_host(src_fb, src_sq, src_count, aov_src, smp_src, aov_dst,
     return _reproject_host(src_fb, src_sq, src_count, aov_src, smp_src, aov_dst, smp_dst, stats, options, True)
 
 
-def _reproject_host(src_fb, src_sq, src_count, aov_src, cam_src, aov_dst, cam_dst, stats, options, samplers):
-    depth = np.ascontiguousarray(aov_dst["depth"], dtype=np.float32)
-    if depth.ndim != 2:
-        raise ValueError("depth must have shape (H, W)")
-    H, W = depth.shape
+def _reproject_host(src_fb, src_sq, src_count, aov_src, view_src, aov_dst, view_dst, stats, options, samplers):
+    _, W, H = _host_frame(aov_dst["depth"], view_dst if samplers else None,
+                          "the destination sampler's frame is not the arrays'")
     n = W * H
-    if samplers and (cam_dst.width, cam_dst.height) != (W, H):
-        raise ValueError("the destination sampler's frame is not the arrays'")
-
-    def arr(a, dtype, per):
-        a = np.ascontiguousarray(a, dtype=dtype)
-        if a.size != n * per:
-            raise ValueError("buffer does not match the frame size")
-        return a
-    fb, sq, count = arr(src_fb, np.float32, 3), arr(src_sq, np.float32, 1), arr(src_count, np.int32, 1)
-    sides = []
-    for aov in (aov_src, aov_dst):
-        tri = aov.get("triangle")
-        sides.append((arr(aov["depth"], np.float32, 1), arr(aov["normal"], np.float32, 3),
-                      None if tri is None else arr(tri, np.int32, 1)))
-    out_fb = np.zeros((H, W, 3), np.float32)
-    out_sq = np.zeros((H, W), np.float32)
-    out_count = np.zeros((H, W), np.int32)
+    sums = [_frame_array(src_fb, np.float32, 3 * n), _frame_array(src_sq, np.float32, n),
+            _frame_array(src_count, np.int32, n)]
+    sides = [[_frame_array(aov[k], _AOVS[k][0], n * _AOVS[k][1]) for k in ("depth", "normal")] +
+             [None if aov.get("triangle") is None else _frame_array(aov["triangle"], np.int32, n)]
+             for aov in (aov_src, aov_dst)]
+    out = (np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.float32), np.zeros((H, W), np.int32))
     st = np.zeros(3, dtype=np.uint64)
     options.pop("stream", None)
     o = reproject_options(**options)
-
-    def opt_ptr(a):
-        return None if a is None else _ptr(a)
-    (s_d, s_n, s_t), (d_d, d_n, d_t) = sides
-    if samplers:
-        ss, sd = _frame_sampler_struct(cam_src), _frame_sampler_struct(cam_dst)
-        check(lib().rt_reproject_sampler_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(s_d), _ptr(s_n), opt_ptr(s_t),
-                                              ctypes.byref(ss), _ptr(d_d), _ptr(d_n), opt_ptr(d_t), ctypes.byref(sd),
-                                              _ptr(out_fb), _ptr(out_sq), _ptr(out_count), _ptr(st), ctypes.byref(o)))
-        out = (out_fb, out_sq, out_count)
-        return out + (dict(zip(REPROJECT_STATS, (int(v) for v in st))),) if stats else out
-    check(lib().rt_reproject_host(_ptr(fb), _ptr(sq), _ptr(count), _ptr(s_d), _ptr(s_n), opt_ptr(s_t), cam_src,
-                                  _ptr(d_d), _ptr(d_n), opt_ptr(d_t), cam_dst, W, H, _ptr(out_fb), _ptr(out_sq),
-                                  _ptr(out_count), _ptr(st), ctypes.byref(o)))
-    out = (out_fb, out_sq, out_count)
-    return out + (dict(zip(REPROJECT_STATS, (int(v) for v in st))),) if stats else out
+    sums_p, src, dst = ([_opt_ptr(a) for a in arrays] for arrays in (sums, sides[0], sides[1]))
+    tail = [_ptr(a) for a in out] + [_ptr(st), ctypes.byref(o)]
+    fn, (v_src, v_dst), size = _frame_entry("rt_reproject", "_host", samplers, (view_src, view_dst), (W, H))
+    check(fn(*sums_p, *src, v_src, *dst, v_dst, *size, *tail))
+    return out + (_stats_dict(REPROJECT_STATS, st),) if stats else out
 
 
 def tonemap_rgb(rgb):
@@ -1328,31 +1261,23 @@ def tonemap_rgb(rgb):
     result) -> (H*W, 4) uint8, row 0 = bottom."""
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
     H, W = rgb.shape[0], rgb.shape[1]
-    n = W * H
-    out = np.zeros((n, 4), dtype=np.uint8)
-    L = lib()
-    with _DeviceBytes(rgb.nbytes) as d_rgb, _DeviceBytes(n * 4) as d_out:
-        check(L.rt_upload(d_rgb, _ptr(rgb), rgb.nbytes))
-        check(L.rt_tonemap_rgb(d_rgb, d_out, W, H, None))
-        check(L.rt_download(_ptr(out), d_out, out.nbytes))
-    return out
+    with DeviceArray(rgb) as d_rgb, DeviceArray((W * H, 4), np.uint8) as d_out:
+        check(lib().rt_tonemap_rgb(d_rgb, d_out, W, H, None))
+        return d_out.read()
 
 
 class DeviceCounters:
     def __init__(self):
-        p = ctypes.c_void_p()
-        check(lib().rt_device_alloc(ctypes.byref(p), N_COUNTERS * 8))
-        self.p = p
-        self.zero()
+        self.words = DeviceArray(N_COUNTERS, np.uint64, zero=True)  # (.read(): the raw counter words)
+        self.p = self.words.p
 
     def zero(self):
-        check(lib().rt_memset(self.p, 0, N_COUNTERS * 8))
+        self.words.zero()
 
     def read(self, finisher=False):
         """The reference-comparable counters; finisher=True adds the wavefront
         finisher's share of node/tri/ray (RT_CNT_FIN_*)."""
-        a = np.zeros(N_COUNTERS, dtype=np.uint64)
-        check(lib().rt_download(_ptr(a), self.p, a.nbytes))
+        a = self.words.read()
         out = {k: int(a[i]) for i, k in enumerate(COUNTER_NAMES)}
         out["deep_push"] = int(a[15])  # RT_CNT_DEEP_PUSH: reference-comparable (the oracle counts it too)
         if finisher:
@@ -1361,24 +1286,16 @@ class DeviceCounters:
 
     def __del__(self):
         try:
-            lib().rt_free(self.p)
+            self.words.free()
         except Exception:
             pass
 
 
 def tonemap(gbuf):
     """draw_frame colour math -> (H*W, 4) uint8, row 0 = bottom."""
-    L = lib()
-    n = gbuf.n
-    d = ctypes.c_void_p()
-    check(L.rt_device_alloc(ctypes.byref(d), n * 4))
-    try:
-        check(L.rt_tonemap(gbuf.g, d, gbuf.width, gbuf.height, None))
-        out = np.zeros((n, 4), dtype=np.uint8)
-        check(L.rt_download(_ptr(out), d, out.nbytes))
-    finally:
-        L.rt_free(d)
-    return out
+    with DeviceArray((gbuf.n, 4), np.uint8) as d:
+        check(lib().rt_tonemap(gbuf.g, d, gbuf.width, gbuf.height, None))
+        return d.read()
 
 
 def save_render(gbuf, path):

@@ -32,25 +32,6 @@ def _stream():
     return s
 
 
-class Dev:
-    """a device buffer holding a numpy array"""
-
-    def __init__(self, a):
-        self.a = np.ascontiguousarray(a)
-        self.p = ctypes.c_void_p()
-        rt.check(rt.lib().rt_device_alloc(ctypes.byref(self.p), max(self.a.nbytes, 16)))
-        if self.a.nbytes:
-            rt.check(rt.lib().rt_upload(self.p, rt._ptr(self.a), self.a.nbytes))
-
-    def read(self):
-        out = np.empty_like(self.a)
-        rt.check(rt.lib().rt_download(rt._ptr(out), self.p, out.nbytes))
-        return out
-
-    def free(self):
-        rt.lib().rt_free(self.p)
-
-
 def _gbuffer(f):
     """the synthetic frame in a rt_gbuffer_create buffer (rt_upload)"""
     H, W = f["depth"].shape
@@ -113,7 +94,7 @@ def test_stream_and_untouched_tail():
             n = W * H
             g = _gbuffer(f)
             fill = np.full(3 * n + 67, np.float32(-7.25))
-            d_out, d_depth, d_normal, d_albedo = Dev(fill), Dev(f["depth"]), Dev(f["normal"]), Dev(f["albedo"])
+            d_out, d_depth, d_normal, d_albedo = (rt.DeviceArray(x) for x in (fill, f["depth"], f["normal"], f["albedo"]))
             try:
                 rt.denoise_device(g.g, (d_depth.p, d_normal.p, d_albedo.p), W, H, d_out.p, stream=s.value)
                 assert _HIP.hipStreamSynchronize(s) == 0
@@ -136,8 +117,8 @@ def test_two_sizes_on_two_streams_equal_alone():
     streams = [_stream(), _stream()]
     frames = [denoise_ref.case(W, H, "defaults") for W, H in shapes]
     gs = [_gbuffer(f) for f, _ in frames]
-    devs = [[Dev(f[k]) for k in ("depth", "normal", "albedo")] for f, _ in frames]
-    outs = [Dev(np.zeros(3 * W * H, F)) for W, H in shapes]
+    devs = [[rt.DeviceArray(f[k]) for k in ("depth", "normal", "albedo")] for f, _ in frames]
+    outs = [rt.DeviceArray(np.zeros(3 * W * H, F)) for W, H in shapes]
     try:
         for (W, H), g, (d_depth, d_normal, d_albedo), d_out, s in zip(shapes, gs, devs, outs, streams):
             rt.denoise_device(g.g, (d_depth.p, d_normal.p, d_albedo.p), W, H, d_out.p, stream=s.value)
@@ -228,11 +209,11 @@ def test_denoise_between_chained_renders(room, coalesce):
     W, H, P = W_REAL, H_REAL, 3
     n = W * H
     s = _stream()
-    d_depth, d_normal, d_albedo = Dev(aov["depth"]), Dev(aov["normal"]), Dev(aov["albedo"])
+    d_depth, d_normal, d_albedo = (rt.DeviceArray(aov[k]) for k in ("depth", "normal", "albedo"))
 
     def frame(mode):
         g = rt.GBuffer(W, H)
-        d_out = Dev(np.zeros(3 * n, F))
+        d_out = rt.DeviceArray(np.zeros(3 * n, F))
         try:
             for k in range(3):
                 opt = rt.options(W, H, P, adaptive=False, kernel=rt.KERNEL_WAVEFRONT, overlap=True,

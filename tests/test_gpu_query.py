@@ -191,24 +191,39 @@ def test_gate_accounting(name, scale):
 
 
 # ------------------------------------------------------------------ 3. shapes
-class Dev:
-    """a device buffer of the C-ABI holding a numpy array's bytes"""
+Dev = rt.DeviceArray  # (the other GPU tests' device buffers too)
 
-    def __init__(self, arr):
-        self.arr = np.ascontiguousarray(arr)
-        self.p = ctypes.c_void_p()
-        rt.check(rt.lib().rt_device_alloc(ctypes.byref(self.p), max(self.arr.nbytes, 16)))
-        if self.arr.nbytes:
-            rt.check(rt.lib().rt_upload(self.p, self.arr.ctypes.data, self.arr.nbytes))
 
-    def read(self):
-        out = np.empty_like(self.arr)
-        if out.nbytes:
-            rt.check(rt.lib().rt_download(out.ctypes.data, self.p, out.nbytes))
-        return out
-
-    def free(self):
-        rt.lib().rt_free(self.p)
+def test_device_array():
+    """rt.DeviceArray: a round trip of an array and of an empty one, zero(), free() twice, the context manager"""
+    a = np.arange(15, dtype=f32).reshape(5, 3)
+    d = rt.DeviceArray(a)
+    assert d.shape == (5, 3) and d.dtype == f32 and d.p.value
+    got = d.read()
+    assert got is not a and got.dtype == f32 and np.array_equal(got, a)
+    d.upload(a[::-1])
+    assert np.array_equal(d.read(), a[::-1])
+    d.zero()
+    assert d.read().shape == (5, 3) and not d.read().any()
+    d.free()
+    d.free()
+    assert not d.p
+    empty = rt.DeviceArray(np.zeros((0, 6), f32))
+    assert empty.p.value and empty.read().shape == (0, 6) and empty.read().dtype == f32
+    empty.zero()
+    empty.free()
+    with rt.DeviceArray(7, np.int32, zero=True) as z:
+        p = z.p.value
+        assert p and z.read().tolist() == [0] * 7
+        view = rt.DeviceArray.at(p + 8, (2,), np.int32)
+        view.upload([5, 6])
+        view.free()  # (not its memory)
+        assert z.read().tolist() == [0, 0, 5, 6, 0, 0, 0]
+    assert not z.p
+    with pytest.raises(ZeroDivisionError):
+        with rt.DeviceArray(3, np.uint8) as z:
+            1 / 0
+    assert not z.p
 
 
 def _guarded(dtype, n):

@@ -33,25 +33,6 @@ def _stream():
     return s
 
 
-class Dev:
-    """a device buffer holding a numpy array"""
-
-    def __init__(self, a):
-        self.a = np.ascontiguousarray(a)
-        self.p = ctypes.c_void_p()
-        rt.check(rt.lib().rt_device_alloc(ctypes.byref(self.p), max(self.a.nbytes, 16)))
-        if self.a.nbytes:
-            rt.check(rt.lib().rt_upload(self.p, rt._ptr(self.a), self.a.nbytes))
-
-    def read(self):
-        out = np.empty_like(self.a)
-        rt.check(rt.lib().rt_download(rt._ptr(out), self.p, out.nbytes))
-        return out
-
-    def free(self):
-        rt.lib().rt_free(self.p)
-
-
 def _assert_same(got, want, what):
     """(fb, sq, count) against (fb, sq, count), any shapes"""
     n = np.asarray(want[2]).size
@@ -123,13 +104,13 @@ def test_writes_only_its_output():
     pad = 192
     src, aov_a, cam_a, aov_b, cam_b, _ = ref.case("small_move", W, H)
     fill = 0x5A5A5A5A
-    d_src = [Dev(a) for a in src]
-    d_a = [Dev(aov_a[k]) for k in ("depth", "normal", "triangle")]
-    d_b = [Dev(aov_b[k]) for k in ("depth", "normal", "triangle")]
-    d_out = [Dev(np.full(pad + n * per + pad, fill, np.uint32)) for per in (3, 1, 1)]
+    d_src = [rt.DeviceArray(a) for a in src]
+    d_a = [rt.DeviceArray(aov_a[k]) for k in ("depth", "normal", "triangle")]
+    d_b = [rt.DeviceArray(aov_b[k]) for k in ("depth", "normal", "triangle")]
+    d_out = [rt.DeviceArray(np.full(pad + n * per + pad, fill, np.uint32)) for per in (3, 1, 1)]
     rng = np.arange(n, dtype=np.uint32) * np.uint32(2654435761)
-    d_rng = Dev(rng)
-    d_stats = Dev(np.asarray([5, 6, 7, fill], np.uint64))
+    d_rng = rt.DeviceArray(rng)
+    d_stats = rt.DeviceArray(np.asarray([5, 6, 7, fill], np.uint64))
     everything = d_src + d_a + d_b + d_out + [d_rng, d_stats]
     try:
         gs = rt.G_Buffer(d_src[0].p, d_src[1].p, d_src[2].p, d_rng.p)
@@ -241,8 +222,8 @@ def test_reproject_behind_chained_renders(room):
     run, _, _, cam_a, aov_a, cam_b, aov_b = room
     W, H, P = W_REAL, H_REAL, 3
     s = _stream()
-    d_a = [Dev(aov_a[k]) for k in ("depth", "normal", "triangle")]
-    d_b = [Dev(aov_b[k]) for k in ("depth", "normal", "triangle")]
+    d_a = [rt.DeviceArray(aov_a[k]) for k in ("depth", "normal", "triangle")]
+    d_b = [rt.DeviceArray(aov_b[k]) for k in ("depth", "normal", "triangle")]
 
     def frame(chained):
         g, out = rt.GBuffer(W, H), rt.GBuffer(W, H)

@@ -29,17 +29,12 @@ usage: python tools/adaptive_bench.py [--scene room2m] [--reps 10] [--warmup 1] 
                                       [--width 1920 --height 1080] [--out FILE]
 """
 import argparse
-import ctypes
-import json
 import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "isaklm-raytracer_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+import gpu_timing
+from gpu_timing import ROOT
 
 import helpers  # noqa: E402
 import rt  # noqa: E402
@@ -63,77 +58,51 @@ def main():
     n = W * H
     test = (a.min_samples, a.tolerance)
 
-    L = rt.lib()
-    if not helpers.gpu_has_device():
-        raise SystemExit("adaptive_bench: no HIP device (nothing is measured without one)")
-    rt.check(L.rt_set_device(0))
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventSynchronize.argtypes = [ctypes.c_void_p]
-    stream, e0, e1 = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
-    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
-
+    gpu_timing.require_device("adaptive_bench")
+    timer = gpu_timing.Timer()
     run = helpers.GpuRun(a.scene)
     seeds = rt.seeds(n)
-
-    def dev(nbytes):
-        p = ctypes.c_void_p()
-        rt.check(L.rt_device_alloc(ctypes.byref(p), max(nbytes, 16)))
-        return p
-
     gb = rt.GBuffer(W, H)  # every variant works on this G_Buffer's four arrays
     g = gb.g
-    d_err, d_cstats, d_pstats = dev(4 * n), dev(32), dev(40)
+    d_err, d_cstats, d_pstats = rt.DeviceArray(n, f32), rt.DeviceArray(4, np.uint64), rt.DeviceArray(5, np.uint64)
     kinds = {"pinhole": rt.Sampler("pinhole", W, H, run.camera), "equirect": rt.Sampler("equirect", W, H, run.camera)}
     variants = [(kind, how) for kind in kinds for how in ("fixed", "adaptive", "render", "converged", "convergence")
                 if not (kind != "pinhole" and how == "render")]
     frames = {}  # kind -> the adaptive frame (fb, sq, count, rng) on the host
     taken = {}   # variant -> samples taken by one launch
 
-    def put_frame(frame):
-        for arr, p in zip(frame, (g.frame_buffer, g.squared_luminance, g.sample_count, g.random_numbers)):
-            rt.check(L.rt_upload(p, arr.ctypes.data, arr.nbytes))
+    def sample(smp, **more):
+        rt.sample_paths_device(run.dev, smp, g.random_numbers, n, g.frame_buffer, g.squared_luminance, g.sample_count,
+                               samples=a.samples, stream=timer.s, stats_ptr=d_pstats, **more)
 
     def launch(v):
         kind, how = v
         smp = kinds[kind]
         if how in ("converged", "convergence"):
-            put_frame(frames[kind])
+            gb.upload(*frames[kind])
         else:
-            rt.check(L.rt_upload(g.random_numbers, seeds.ctypes.data, 4 * n))
-        rt.check(L.rt_memset(d_pstats, 0, 40))
-        rt.check(L.rt_memset(d_cstats, 0, 32))
-        t0 = time.perf_counter()
-        assert hip.hipEventRecord(e0, stream) == 0
-        if how == "fixed":
-            rt.sample_paths_device(run.dev, smp, g.random_numbers, n, g.frame_buffer, g.squared_luminance, g.sample_count,
-                                   samples=a.samples, stream=stream.value, stats_ptr=d_pstats)
-        elif how == "adaptive":
-            rt.sample_paths_device(run.dev, smp, g.random_numbers, n, g.frame_buffer, g.squared_luminance, g.sample_count,
-                                   samples=a.samples, stream=stream.value, stats_ptr=d_pstats, adaptive=test)
-        elif how == "converged":
-            rt.sample_paths_device(run.dev, smp, g.random_numbers, n, g.frame_buffer, g.squared_luminance, g.sample_count,
-                                   samples=a.samples, accumulate=True, stream=stream.value, stats_ptr=d_pstats,
-                                   adaptive=(a.min_samples, 1e9))
-        elif how == "convergence":
-            rt.convergence_device(g.frame_buffer, g.squared_luminance, g.sample_count, n, a.min_samples, a.tolerance,
-                                  d_err, d_cstats, stream=stream.value)
-        else:
-            opt = rt.options(W, H, a.samples, adaptive=True, min_samples=a.min_samples, tolerance=a.tolerance,
-                             kernel=rt.KERNEL_WAVEFRONT, stream=stream.value)
-            rt.render(run.dev, gb, run.camera, 0, opt)
-            rt.join(stream.value)
-        assert hip.hipEventRecord(e1, stream) == 0
-        assert hip.hipEventSynchronize(e1) == 0
-        wall = (time.perf_counter() - t0) * 1e3
-        ms = ctypes.c_float()
-        assert hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1) == 0
-        st = np.zeros(5, np.uint64)
-        rt.check(L.rt_download(st.ctypes.data, d_pstats, 40))
-        taken[v] = int(st[1])
-        return ms.value, wall
+            gb.array("random_numbers").upload(seeds)
+        d_pstats.zero()
+        d_cstats.zero()
+
+        def work():
+            if how == "fixed":
+                sample(smp)
+            elif how == "adaptive":
+                sample(smp, adaptive=test)
+            elif how == "converged":
+                sample(smp, accumulate=True, adaptive=(a.min_samples, 1e9))
+            elif how == "convergence":
+                rt.convergence_device(g.frame_buffer, g.squared_luminance, g.sample_count, n, a.min_samples, a.tolerance,
+                                      d_err, d_cstats, stream=timer.s)
+            else:
+                opt = rt.options(W, H, a.samples, adaptive=True, min_samples=a.min_samples, tolerance=a.tolerance,
+                                 kernel=rt.KERNEL_WAVEFRONT, stream=timer.s)
+                rt.render(run.dev, gb, run.camera, 0, opt)
+                rt.join(timer.s)
+        ms, wall = timer.span(work)
+        taken[v] = int(d_pstats.read()[1])
+        return ms, wall
 
     # before any timing: the adaptive frames, and the pinhole one against rt_render's
     for kind in kinds:
@@ -149,34 +118,24 @@ def main():
         assert np.array_equal(arr.view(np.uint32), ref.view(np.uint32)), f"pinhole adaptive: {what} differs from rt_render"
     taken[("pinhole", "render")] = int(frames["pinhole"][2].sum())
 
-    for _ in range(a.warmup):
-        for v in variants:
-            launch(v)
-    times = {v: [] for v in variants}
-    for _ in range(a.reps):
-        for v in variants:
-            times[v].append(launch(v))
+    times = gpu_timing.interleaved(variants, launch, a.warmup, a.reps)
     taken[("pinhole", "render")] = int(frames["pinhole"][2].sum())
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for v in variants:
-            t = np.array([x[0] for x in times[v]])
-            wall = np.array([x[1] for x in times[v]])
-            med = float(np.median(t))
-            base = float(np.median([x[0] for x in times[(v[0], "fixed")]]))
-            cnt = frames[v[0]][2]
-            rec = {"scene": a.scene, "sampler": v[0], "variant": v[1], "width": W, "height": H, "samples": a.samples,
-                   "min_samples": a.min_samples, "tolerance": a.tolerance, "reps": a.reps, "ms_median": round(med, 3),
-                   "ms_min": round(float(t.min()), 3), "ms_max": round(float(t.max()), 3),
-                   "spread": round(float(t.max() - t.min()) / med, 4), "host_ms_median": round(float(np.median(wall)), 3),
-                   "samples_taken": taken[v], "mean_samples_per_pixel": round(taken[v] / n, 3),
-                   "time_over_fixed": round(med / base, 4)}
-            if v[1] == "adaptive":
-                rec["pixels_stopped_at_min"] = int((cnt == a.min_samples).sum())
-                rec["pixels_never_stopped"] = int((cnt == a.samples).sum())
-            line = json.dumps(rec)
-            print(line, flush=True)
-            f.write(line + "\n")
+    records = []
+    for v in variants:
+        t = [x[0] for x in times[v]]
+        med = float(np.median(t))
+        base = float(np.median([x[0] for x in times[(v[0], "fixed")]]))
+        cnt = frames[v[0]][2]
+        rec = {"scene": a.scene, "sampler": v[0], "variant": v[1], "width": W, "height": H, "samples": a.samples,
+               "min_samples": a.min_samples, "tolerance": a.tolerance, **gpu_timing.summary(t, 3),
+               "host_ms_median": round(float(np.median([x[1] for x in times[v]])), 3),
+               "samples_taken": taken[v], "mean_samples_per_pixel": round(taken[v] / n, 3),
+               "time_over_fixed": round(med / base, 4)}
+        if v[1] == "adaptive":
+            rec["pixels_stopped_at_min"] = int((cnt == a.min_samples).sum())
+            rec["pixels_never_stopped"] = int((cnt == a.samples).sum())
+        records.append(rec)
+    gpu_timing.write_lines(a.out, records)
 
 
 if __name__ == "__main__":

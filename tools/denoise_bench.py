@@ -18,13 +18,13 @@ Prints one JSON object (also written to FILE).
 import ctypes
 import json
 import os
-import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in ("isaklm-raytracer_amd", "tests", "oracle"):
-    sys.path.insert(0, os.path.join(ROOT, p))
+import numpy as np
+
+import gpu_timing
+
 import helpers  # noqa: E402
 import rt  # noqa: E402
 
@@ -42,8 +42,8 @@ def traffic_bytes(pixels, iterations):
 
 
 def spread(ms):
-    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4),
-            "reps": len(ms)}
+    s = gpu_timing.summary(ms, 4)
+    return {"median_ms": s["ms_median"], "min_ms": s["ms_min"], "max_ms": s["ms_max"], "reps": s["reps"]}
 
 
 def main():
@@ -56,35 +56,29 @@ def main():
     scene = args[0] if args else "room_small"
     W, H = (int(args[1]), int(args[2])) if len(args) >= 3 else (1920, 1080)
     n = W * H
-    if not helpers.gpu_has_device():
-        sys.exit("denoise_bench: no GPU (a timing needs one)")
-    hip = ctypes.CDLL("libamdhip64.so")
+    gpu_timing.require_device("denoise_bench")
     L = rt.lib()
     run = helpers.GpuRun(scene)
     g = rt.GBuffer(W, H)
     rt.render(run.dev, g, run.camera, 0, rt.options(W, H, 4, adaptive=False, kernel=rt.KERNEL_WAVEFRONT))
     rt.join()
-
-    def alloc(nbytes):
-        p = ctypes.c_void_p()
-        rt.check(L.rt_device_alloc(ctypes.byref(p), nbytes))
-        return p
-    d_depth, d_normal, d_albedo, d_out = alloc(n * 4), alloc(n * 12), alloc(n * 12), alloc(n * 12)
-    b = rt.RtAovBuffers(d_depth, d_normal, d_albedo, None)
+    f32 = np.float32
+    d_depth, d_normal, d_albedo = rt.DeviceArray(n, f32), rt.DeviceArray((n, 3), f32), rt.DeviceArray((n, 3), f32)
+    d_out = rt.DeviceArray((n, 3), f32)
+    b = rt.RtAovBuffers(d_depth.p, d_normal.p, d_albedo.p, None)
     rt.check(L.rt_render_aov(run.dev.prepared, run.camera, W, H, ctypes.byref(b), None))
-    s = ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(s)) == 0
+    timer = gpu_timing.Timer()
 
     result = {"scene": scene, "width": W, "height": H, "batch": BATCH, "hbm_tb_s": HBM_TBS, "denoise": {}}
     for iterations in (1, 2, 3, 4, 5):
         ms = []
-        for r in range(WARMUP + REPS):
-            assert hip.hipStreamSynchronize(s) == 0
+        for r in range(WARMUP + REPS):  # (a host-clock batch: a launch returns before its kernels finish)
+            timer.synchronize()
             t = time.perf_counter()
             for _ in range(BATCH):
                 rt.denoise_device(g.g, (d_depth, d_normal, d_albedo), W, H, d_out, iterations=iterations,
-                                  stream=s.value)
-            assert hip.hipStreamSynchronize(s) == 0
+                                  stream=timer.s)
+            timer.synchronize()
             if r >= WARMUP:
                 ms.append((time.perf_counter() - t) * 1e3 / BATCH)
         e = spread(ms)
@@ -111,9 +105,9 @@ def main():
     result["render_1spp"] = spread(ms)
     result["denoise_over_render_1spp"] = round(d5 / result["render_1spp"]["median_ms"], 3)
 
-    assert hip.hipStreamDestroy(s) == 0
-    for p in (d_depth, d_normal, d_albedo, d_out):
-        L.rt_free(p)
+    timer.close()
+    for d in (d_depth, d_normal, d_albedo, d_out):
+        d.free()
     g.free()
     line = json.dumps(result)
     print(line)

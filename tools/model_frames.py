@@ -32,22 +32,23 @@ usage: python tools/model_frames.py [--model equirect] [--scene room_small] [--w
        python tools/model_frames.py --bench [--scene room2m] [--reps 10] [--warmup 2] [--out FILE]
 """
 import argparse
+import collections
 import ctypes
 import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "isaklm-raytracer_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+import gpu_timing
+from gpu_timing import ROOT
 
 import helpers  # noqa: E402
 import rt  # noqa: E402
 
 f32 = np.float32
 AOV = ("depth", "normal", "albedo", "triangle")
+# a timed variant: its comparison group, what sets its frame up (outside the span), the timed call, record fields
+Variant = collections.namedtuple("Variant", "group prepare fn fields")
 
 
 def model_sampler(run, kind, W, H, move=(0.0, 0.0, 0.0)):
@@ -101,37 +102,26 @@ def flow(a):
 
 def bench(a):
     L = rt.lib()
-    if not helpers.gpu_has_device():
-        raise SystemExit("model_frames: no HIP device (nothing is measured without one)")
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventSynchronize.argtypes = [ctypes.c_void_p]
-    stream, e0, e1 = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
-    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
+    gpu_timing.require_device("model_frames")
+    timer = gpu_timing.Timer()
+    stream = timer.stream
     run = helpers.GpuRun(a.scene)
     sizes = {"equirect": (1920, 960), "fisheye": (1920, 1080), "pinhole": (1920, 1080), "ortho": (1920, 1080)}
     n_max = 1920 * 1080
 
-    def dev(nbytes):
-        p = ctypes.c_void_p()
-        rt.check(L.rt_device_alloc(ctypes.byref(p), max(nbytes, 16)))
-        return p
-
     def aov_buffers():
-        return [dev(4 * n_max), dev(12 * n_max), dev(12 * n_max), dev(4 * n_max)]
+        return [rt.DeviceArray(n_max * per, dtype) for per, dtype in ((1, f32), (3, f32), (3, f32), (1, np.int32))]
 
     aov_a, aov_b, aov_c = aov_buffers(), aov_buffers(), aov_buffers()  # camera A, camera B, the composition's
-    d_rays, d_hits, d_surf, d_rgb = dev(24 * n_max), dev(16 * n_max), dev(80 * n_max), dev(12 * n_max)
+    d_rays, d_rgb = rt.DeviceArray((n_max, 6), f32), rt.DeviceArray((n_max, 3), f32)
+    d_hits, d_surf = rt.DeviceArray(n_max, rt.RAY_HIT), rt.DeviceArray(n_max, rt.RAY_SURFACE)
     g, g_out = rt.GBuffer(1920, 1080), rt.GBuffer(1920, 1080)
 
-    def read(p, count, dtype):
-        out = np.zeros(count, dtype)
-        rt.check(L.rt_download(out.ctypes.data, p, out.nbytes))
-        return out
+    def read(d, count, dtype):
+        """the first `count` values of a device array"""
+        return rt.DeviceArray.at(d, count, dtype).read()
 
-    variants = {}  # name -> (group, launch function, record fields)
+    variants = {}  # name -> Variant
     for kind, (W, H) in sizes.items():
         n = W * H
         sa, sb = model_sampler(run, kind, W, H), model_sampler(run, kind, W, H, (0.04, 0.03, 0.02))
@@ -153,32 +143,32 @@ def bench(a):
                 s = sa.struct()
                 rt.check(L.rt_sampler_rays(ctypes.byref(s), None, n, d_rays, stream))
                 rt.trace_rays_device(run.dev, d_rays, n, d_hits, d_surf, stream=stream.value)
-            variants[f"sample_aov/{kind}/rt_sample_aov"] = ("sample_aov/" + kind, prepare, fused, fields)
-            variants[f"sample_aov/{kind}/rays+trace"] = ("sample_aov/" + kind, prepare, composed, fields)
+            variants[f"sample_aov/{kind}/rt_sample_aov"] = Variant("sample_aov/" + kind, prepare, fused, fields)
+            variants[f"sample_aov/{kind}/rays+trace"] = Variant("sample_aov/" + kind, prepare, composed, fields)
         if kind == "equirect":
             def dn_sampler(sa=sa):
                 rt.denoise_sampler_device(g.g, aov_a[:3], sa, d_rgb, stream=stream.value)
 
             def dn_plain(W=W, H=H):
                 rt.denoise_device(g.g, aov_a[:3], W, H, d_rgb, stream=stream.value)
-            variants["denoise/equirect/rt_denoise_sampler"] = ("denoise/equirect", prepare, dn_sampler, fields)
-            variants["denoise/equirect/rt_denoise"] = ("denoise/equirect", prepare, dn_plain, fields)
+            variants["denoise/equirect/rt_denoise_sampler"] = Variant("denoise/equirect", prepare, dn_sampler, fields)
+            variants["denoise/equirect/rt_denoise"] = Variant("denoise/equirect", prepare, dn_plain, fields)
 
         def rp_sampler(sa=sa, sb=sb):
             rt.reproject_sampler_device(g.g, rp(aov_a), sa, rp(aov_b), sb, g_out.g, stream=stream.value)
 
         def rp_plain(sa=sa, sb=sb, W=W, H=H):
             rt.reproject_device(g.g, rp(aov_a), sa.camera, rp(aov_b), sb.camera, W, H, g_out.g, stream=stream.value)
-        variants[f"reproject/{kind}/rt_reproject_sampler"] = ("reproject/" + kind, prepare, rp_sampler, fields)
-        variants[f"reproject/{kind}/rt_reproject"] = ("reproject/" + kind, prepare, rp_plain, fields)
+        variants[f"reproject/{kind}/rt_reproject_sampler"] = Variant("reproject/" + kind, prepare, rp_sampler, fields)
+        variants[f"reproject/{kind}/rt_reproject"] = Variant("reproject/" + kind, prepare, rp_plain, fields)
 
     # the fused AOV pass must be the composition before the two are compared
     for kind in ("equirect", "fisheye"):
         _, prepare, fused, fields = variants[f"sample_aov/{kind}/rt_sample_aov"]
         n = fields["width"] * fields["height"]
-        variants[f"sample_aov/{kind}/rays+trace"][2]()
+        variants[f"sample_aov/{kind}/rays+trace"].fn()
         fused()
-        assert hip.hipStreamSynchronize(stream) == 0
+        timer.synchronize()
         surf = read(d_surf, n, rt.RAY_SURFACE)
         hits = read(d_hits, n, rt.RAY_HIT)
         for got, want, what in ((read(aov_c[0], n, f32), surf["t"], "depth"), (read(aov_c[1], 3 * n, f32), surf["normal"], "normal"),
@@ -187,39 +177,20 @@ def bench(a):
             want = np.ascontiguousarray(want).reshape(-1)
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{kind}: {what} differs"
 
-    def launch(name):
-        _, _, fn, _ = variants[name]
-        assert hip.hipEventRecord(e0, stream) == 0
-        fn()
-        assert hip.hipEventRecord(e1, stream) == 0
-        assert hip.hipEventSynchronize(e1) == 0
-        ms = ctypes.c_float()
-        assert hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1) == 0
-        return ms.value
-
     # one size at a time: its frame and guides are made once, its variants alternate
-    times = {name: [] for name in variants}
+    times = {}
     for kind in sizes:
         names = [name for name in variants if name.split("/")[1] == kind]
-        variants[names[0]][1]()
+        variants[names[0]].prepare()
         rt.check(L.rt_synchronize())
-        for r in range(a.warmup + a.reps):
-            for name in names:
-                t = launch(name)
-                if r >= a.warmup:
-                    times[name].append(t)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for name, (group, _, _, fields) in variants.items():
-            t = np.asarray(times[name])
-            med = float(np.median(t))
-            base = float(np.median(times[[x for x in variants if variants[x][0] == group][-1]]))
-            rec = dict(scene=a.scene, call=name.split("/")[0], variant=name.split("/")[2], **fields, reps=a.reps,
-                       ms_median=round(med, 4), ms_min=round(float(t.min()), 4), ms_max=round(float(t.max()), 4),
-                       time_over_baseline=round(med / base, 4))
-            line = json.dumps(rec)
-            print(line, flush=True)
-            f.write(line + "\n")
+        times.update(gpu_timing.interleaved(names, lambda name: timer.span(variants[name].fn)[0], a.warmup, a.reps))
+    records = []
+    for name, (group, _, _, fields) in variants.items():
+        med = float(np.median(times[name]))
+        base = float(np.median(times[[x for x in variants if variants[x].group == group][-1]]))
+        records.append(dict(scene=a.scene, call=name.split("/")[0], variant=name.split("/")[2], **fields,
+                            **gpu_timing.summary(times[name], 4), time_over_baseline=round(med / base, 4)))
+    gpu_timing.write_lines(a.out, records)
 
 
 def main():

@@ -27,17 +27,16 @@ usage: python tools/occlusion_bench.py [--scene room2m] [--reps 20] [--warmup 3]
                                        [--width 1920 --height 1080] [--out FILE] [--count-lib PATH]
 """
 import argparse
-import ctypes
+import contextlib
 import json
 import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "isaklm-raytracer_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+import gpu_timing
+from gpu_timing import ROOT
 
 import helpers  # noqa: E402
 import rt  # noqa: E402
@@ -81,20 +80,17 @@ def ray_sets(run, width, height):
 
 def count_early(a):
     """child mode (the counting build is loaded through ISAKLM_RT_LIB_OVERRIDE): prints {set: early share}"""
-    L = rt.lib()
-    rt.check(L.rt_set_device(0))
+    gpu_timing.require_device("occlusion_bench")
     run = helpers.GpuRun(a.scene)
     out = {}
     for name, (rays, tmax) in ray_sets(run, a.width, a.height).items():
-        st = np.zeros(4, np.uint64)
-        with rt._DeviceBytes(rays.nbytes) as d_rays, rt._DeviceBytes(4 * len(rays)) as d_tmax, \
-                rt._DeviceBytes(len(rays)) as d_out, rt._DeviceBytes(st.nbytes) as d_st:
-            rt.check(L.rt_upload(d_rays, rays.ctypes.data, rays.nbytes))
-            if tmax is not None:
-                rt.check(L.rt_upload(d_tmax, tmax.ctypes.data, tmax.nbytes))
-            rt.check(L.rt_memset(d_st, 0, st.nbytes))
-            rt.occluded_device(run.dev, d_rays, d_tmax if tmax is not None else None, len(rays), d_out, stats_ptr=d_st)
-            rt.check(L.rt_download(st.ctypes.data, d_st, st.nbytes))
+        with contextlib.ExitStack() as stack:
+            put = stack.enter_context
+            d_rays, d_out = put(rt.DeviceArray(rays)), put(rt.DeviceArray(len(rays), np.uint8))
+            d_st = put(rt.DeviceArray(4, np.uint64, zero=True))
+            d_tmax = put(rt.DeviceArray(tmax)) if tmax is not None else None
+            rt.occluded_device(run.dev, d_rays, d_tmax, len(rays), d_out, stats_ptr=d_st)
+            st = d_st.read()
         assert int(st[0]) == len(rays)
         out[name] = round(int(st[3]) / len(rays), 4)
     print("EARLY " + json.dumps(out), flush=True)
@@ -124,43 +120,23 @@ def main():
             sys.exit("the counting build's run failed:\n" + r.stdout[-2000:] + r.stderr[-2000:])
         early = json.loads(lines[-1][6:])
 
-    L = rt.lib()
-    rt.check(L.rt_set_device(0))
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventSynchronize.argtypes = [ctypes.c_void_p]
-    stream, e0, e1 = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
-    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
-
+    gpu_timing.require_device("occlusion_bench")
+    timer = gpu_timing.Timer()
     run = helpers.GpuRun(a.scene)
     sets = ray_sets(run, a.width, a.height)
-
-    def dev(arr):
-        p = ctypes.c_void_p()
-        rt.check(L.rt_device_alloc(ctypes.byref(p), max(arr.nbytes, 16)))
-        rt.check(L.rt_upload(p, arr.ctypes.data, arr.nbytes))
-        return p
-
     bufs = {}
     for k, (rays, tmax) in sets.items():
-        bufs[k] = {"rays": dev(rays), "tmax": dev(tmax) if tmax is not None else None, "n": len(rays),
-                   "hits": dev(np.zeros(len(rays), rt.RAY_HIT)), "occ": dev(np.zeros(len(rays), np.uint8))}
+        bufs[k] = {"rays": rt.DeviceArray(rays), "tmax": rt.DeviceArray(tmax) if tmax is not None else None,
+                   "n": len(rays), "hits": rt.DeviceArray(len(rays), rt.RAY_HIT, zero=True),
+                   "occ": rt.DeviceArray(len(rays), np.uint8, zero=True)}
     variants = [(k, call) for k in sets for call in ("rt_trace_rays", "rt_occluded")]
 
     def launch(v, tmax=True):
         b = bufs[v[0]]
-        assert hip.hipEventRecord(e0, stream) == 0
         if v[1] == "rt_trace_rays":
-            rt.trace_rays_device(run.dev, b["rays"], b["n"], b["hits"], stream=stream.value)
-        else:
-            rt.occluded_device(run.dev, b["rays"], b["tmax"] if tmax else None, b["n"], b["occ"], stream=stream.value)
-        assert hip.hipEventRecord(e1, stream) == 0
-        assert hip.hipEventSynchronize(e1) == 0
-        ms = ctypes.c_float()
-        assert hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1) == 0
-        return ms.value
+            return timer.span(lambda: rt.trace_rays_device(run.dev, b["rays"], b["n"], b["hits"], stream=timer.s))[0]
+        return timer.span(lambda: rt.occluded_device(run.dev, b["rays"], b["tmax"] if tmax else None, b["n"], b["occ"],
+                                                     stream=timer.s))[0]
 
     # the two calls must agree before they are compared: without a tmax rt_occluded is the hit flag
     frac = {}
@@ -168,42 +144,28 @@ def main():
         b = bufs[k]
         launch((k, "rt_trace_rays"))
         launch((k, "rt_occluded"), tmax=False)
-        h, o = np.zeros(b["n"], rt.RAY_HIT), np.zeros(b["n"], np.uint8)
-        rt.check(L.rt_download(h.ctypes.data, b["hits"], h.nbytes))
-        rt.check(L.rt_download(o.ctypes.data, b["occ"], o.nbytes))
+        h, o = b["hits"].read(), b["occ"].read()
         assert np.array_equal(o, (h["triangle"] >= 0).astype(np.uint8)), k
         launch((k, "rt_occluded"))
-        rt.check(L.rt_download(o.ctypes.data, b["occ"], o.nbytes))
+        o = b["occ"].read()
         assert not (o & ~(h["triangle"] >= 0)).any(), k  # occluded implies hit
         frac[k] = (float((h["triangle"] >= 0).mean()), float(o.mean()))
-    for _ in range(a.warmup):
-        for v in variants:
-            launch(v)
-    times = {v: [] for v in variants}
-    for _ in range(a.reps):
-        for v in variants:
-            times[v].append(launch(v))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for k in sets:
-            base = np.array(times[(k, "rt_trace_rays")])
-            base_spread = float(base.max() - base.min())
-            for call in ("rt_trace_rays", "rt_occluded"):
-                t = np.array(times[(k, call)])
-                med = float(np.median(t))
-                rec = {"scene": a.scene, "set": k, "call": call, "rays": bufs[k]["n"], "reps": a.reps,
-                       "ms_median": round(med, 4), "ms_min": round(float(t.min()), 4), "ms_max": round(float(t.max()), 4),
-                       "spread": round(float(t.max() - t.min()) / med, 4),
-                       "mrays_per_s_median": round(bufs[k]["n"] / med / 1e3, 1),
-                       "hit_fraction": round(frac[k][0], 4)}
-                if call == "rt_occluded":
-                    rec["occluded_fraction"] = round(frac[k][1], 4)
-                    rec["speedup_over_trace_rays"] = round(float(np.median(base)) / med, 3)
-                    rec["not_slower_within_trace_rays_spread"] = bool(med <= float(np.median(base)) + base_spread)
-                    rec["early_share"] = early[k] if early else None
-                line = json.dumps(rec)
-                print(line, flush=True)
-                f.write(line + "\n")
+    times = gpu_timing.interleaved(variants, launch, a.warmup, a.reps)
+    records = []
+    for k in sets:
+        base = np.array(times[(k, "rt_trace_rays")])
+        base_spread = float(base.max() - base.min())
+        for call in ("rt_trace_rays", "rt_occluded"):
+            med = float(np.median(times[(k, call)]))
+            rec = {"scene": a.scene, "set": k, "call": call, "rays": bufs[k]["n"], **gpu_timing.summary(times[(k, call)], 4),
+                   "mrays_per_s_median": round(bufs[k]["n"] / med / 1e3, 1), "hit_fraction": round(frac[k][0], 4)}
+            if call == "rt_occluded":
+                rec["occluded_fraction"] = round(frac[k][1], 4)
+                rec["speedup_over_trace_rays"] = round(float(np.median(base)) / med, 3)
+                rec["not_slower_within_trace_rays_spread"] = bool(med <= float(np.median(base)) + base_spread)
+                rec["early_share"] = early[k] if early else None
+            records.append(rec)
+    gpu_timing.write_lines(a.out, records)
 
 
 if __name__ == "__main__":

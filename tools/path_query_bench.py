@@ -21,16 +21,12 @@ usage: python tools/path_query_bench.py [--scene room2m] [--reps 20] [--warmup 3
                                         [--width 1920 --height 1080] [--out FILE]
 """
 import argparse
-import ctypes
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "isaklm-raytracer_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+import gpu_timing
+from gpu_timing import ROOT
 
 import helpers  # noqa: E402
 import path_query_ref  # noqa: E402
@@ -51,19 +47,12 @@ def main():
     W, H = a.width, a.height
     n = W * H
 
-    L = rt.lib()
-    rt.check(L.rt_set_device(0))
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventSynchronize.argtypes = [ctypes.c_void_p]
-    stream, e0, e1 = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
-    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
-
+    gpu_timing.require_device("path_query_bench")
+    timer = gpu_timing.Timer()
     run = helpers.GpuRun(a.scene)
     gbuf = rt.GBuffer(W, H)
-    seeds = gbuf.download()[3]
+    gbuf_rng = gbuf.array("random_numbers")
+    seeds = gbuf_rng.read()
     cam_rays, cam_rng = path_query_ref.camera_samples(np.asarray(run.camera.as_list(), f32), W, H, seeds)
     raw, ntris = run.host.triangles_bytes()
     verts = np.frombuffer(raw, np.uint8).reshape(ntris, rt.TRIANGLE_BYTES)[:, :36].copy().view(f32).reshape(-1, 3)
@@ -73,14 +62,9 @@ def main():
                                d / np.linalg.norm(d, axis=1)[:, None]], axis=1).astype(f32)
     sets = {"camera": (cam_rays, cam_rng), "incoherent": (inc_rays, seeds)}
 
-    def dev(arr):
-        p = ctypes.c_void_p()
-        rt.check(L.rt_device_alloc(ctypes.byref(p), max(arr.nbytes, 16)))
-        rt.check(L.rt_upload(p, arr.ctypes.data, arr.nbytes))
-        return p
-
-    bufs = {k: {"rays": dev(r), "rng": dev(s), "rad": dev(np.zeros((n, 3), f32)), "sq": dev(np.zeros(n, f32)),
-                "stats": dev(np.zeros(5, np.uint64))} for k, (r, s) in sets.items()}
+    bufs = {k: {"rays": rt.DeviceArray(r), "rng": rt.DeviceArray(s), "rad": rt.DeviceArray((n, 3), f32, zero=True),
+                "sq": rt.DeviceArray(n, f32, zero=True), "stats": rt.DeviceArray(5, np.uint64, zero=True)}
+            for k, (r, s) in sets.items()}
     variants = [("rt_trace_paths", "camera"), ("rt_trace_paths", "incoherent"), ("rt_render mega", "camera"),
                 ("rt_render wavefront", "camera")]
 
@@ -88,23 +72,21 @@ def main():
         call, name = v
         if call == "rt_trace_paths":  # (the launch's RNG states: the set's own)
             b = bufs[name]
-            rt.check(L.rt_upload(b["rng"], sets[name][1].ctypes.data, 4 * n))
+            b["rng"].upload(sets[name][1])
+
+            def work():
+                rt.trace_paths_device(run.dev, b["rays"], b["rng"], n, b["rad"], b["sq"], stream=timer.s,
+                                      stats_ptr=b["stats"] if stats else None)
         else:
-            rt.check(L.rt_upload(gbuf.g.random_numbers, seeds.ctypes.data, 4 * n))
-            opt = rt.options(W, H, 1, adaptive=False, stream=stream.value,
+            gbuf_rng.upload(seeds)
+            opt = rt.options(W, H, 1, adaptive=False, stream=timer.s,
                              kernel=rt.KERNEL_MEGA if call == "rt_render mega" else rt.KERNEL_WAVEFRONT)
-        assert hip.hipEventRecord(e0, stream) == 0
-        if call == "rt_trace_paths":
-            rt.trace_paths_device(run.dev, b["rays"], b["rng"], n, b["rad"], b["sq"], stream=stream.value,
-                                  stats_ptr=b["stats"] if stats else None)
-        else:
-            rt.render(run.dev, gbuf, run.camera, 0, opt)
-        assert hip.hipEventRecord(e1, stream) == 0
-        assert hip.hipEventSynchronize(e1) == 0
+
+            def work():
+                rt.render(run.dev, gbuf, run.camera, 0, opt)
+        ms = timer.span(work)[0]
         rt.join()
-        ms = ctypes.c_float()
-        assert hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1) == 0
-        return ms.value
+        return ms
 
     # the query on the camera samples must be the megakernel's pass before the two are compared
     launch(("rt_render mega", "camera"))
@@ -114,42 +96,27 @@ def main():
     for name in sets:
         b = bufs[name]
         launch(("rt_trace_paths", name), stats=True)
-        st = np.zeros(5, np.uint64)
-        rt.check(L.rt_download(st.ctypes.data, b["stats"], st.nbytes))
-        counted[name] = dict(zip(rt.PATH_STATS, (int(x) for x in st)))
+        counted[name] = dict(zip(rt.PATH_STATS, (int(x) for x in b["stats"].read())))
         assert counted[name]["rays"] == n and counted[name]["paths"] == n
-    got = [np.zeros((n, 3), f32), np.zeros(n, f32), np.zeros(n, np.uint32)]
-    for arr, key in zip(got, ("rad", "sq", "rng")):
-        rt.check(L.rt_download(arr.ctypes.data, bufs["camera"][key], arr.nbytes))
+    got = [bufs["camera"][key].read() for key in ("rad", "sq", "rng")]
     for arr, want, what in zip(got, (fb, sq, rng), ("radiance", "sq", "rng")):
         assert np.array_equal(arr.view(np.uint32), want.view(np.uint32)), f"{what} differs from the megakernel's pass"
 
-    for _ in range(a.warmup):
-        for v in variants:
-            launch(v)
-    times = {v: [] for v in variants}
-    for _ in range(a.reps):
-        for v in variants:
-            times[v].append(launch(v))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    times = gpu_timing.interleaved(variants, launch, a.warmup, a.reps)
     base = float(np.median(times[("rt_render mega", "camera")]))
-    with open(a.out, "w") as f:
-        for v in variants:
-            t = np.array(times[v])
-            med = float(np.median(t))
-            rec = {"scene": a.scene, "call": v[0], "set": v[1], "paths": n, "reps": a.reps,
-                   "ms_median": round(med, 4), "ms_min": round(float(t.min()), 4), "ms_max": round(float(t.max()), 4),
-                   "spread": round(float(t.max() - t.min()) / med, 4), "mpaths_per_s_median": round(n / med / 1e3, 2),
-                   "time_over_megakernel": round(med / base, 3)}
-            if v[0] == "rt_trace_paths":
-                c = counted[v[1]]
-                rec["trace_calls_per_path"] = round(c["trace_calls"] / n, 3)
-                rec["longest_path"] = c["max_depth"]
-                if v[1] == "camera":
-                    rec["equals_megakernel_pass_bitwise"] = True
-            line = json.dumps(rec)
-            print(line, flush=True)
-            f.write(line + "\n")
+    records = []
+    for v in variants:
+        med = float(np.median(times[v]))
+        rec = {"scene": a.scene, "call": v[0], "set": v[1], "paths": n, **gpu_timing.summary(times[v], 4),
+               "mpaths_per_s_median": round(n / med / 1e3, 2), "time_over_megakernel": round(med / base, 3)}
+        if v[0] == "rt_trace_paths":
+            c = counted[v[1]]
+            rec["trace_calls_per_path"] = round(c["trace_calls"] / n, 3)
+            rec["longest_path"] = c["max_depth"]
+            if v[1] == "camera":
+                rec["equals_megakernel_pass_bitwise"] = True
+        records.append(rec)
+    gpu_timing.write_lines(a.out, records)
 
 
 if __name__ == "__main__":

@@ -17,16 +17,12 @@ usage: python tools/ray_query_bench.py [--scene room2m] [--reps 20] [--warmup 3]
                                        [--width 1920 --height 1080] [--out FILE]
 """
 import argparse
-import ctypes
-import json
 import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "isaklm-raytracer_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+import gpu_timing
+from gpu_timing import ROOT
 
 import helpers  # noqa: E402
 import rt  # noqa: E402
@@ -42,17 +38,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ray_query", "ray_query_bench.jsonl"))
     a = ap.parse_args()
 
-    L = rt.lib()
-    rt.check(L.rt_set_device(0))
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventSynchronize.argtypes = [ctypes.c_void_p]
-    hip.hipStreamSynchronize.argtypes = [ctypes.c_void_p]
-    stream, e0, e1 = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
-    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
-
+    gpu_timing.require_device("ray_query_bench")
+    timer = gpu_timing.Timer()
     run = helpers.GpuRun(a.scene)
     cam_rays = rt.camera_rays(run.camera, a.width, a.height)
     hits, surf = rt.trace_rays(run.dev, cam_rays, surface=True)
@@ -63,13 +50,7 @@ def main():
     bounce = np.concatenate([surf["position"][ok], d.astype(np.float32)], axis=1).astype(np.float32)
     sets = {"camera": cam_rays, "bounce": bounce}
 
-    def dev(arr):
-        p = ctypes.c_void_p()
-        rt.check(L.rt_device_alloc(ctypes.byref(p), max(arr.nbytes, 16)))
-        rt.check(L.rt_upload(p, arr.ctypes.data, arr.nbytes))
-        return p
-
-    bufs = {k: (dev(v), dev(np.zeros(len(v), rt.RAY_HIT)), len(v)) for k, v in sets.items()}
+    bufs = {k: (rt.DeviceArray(v), rt.DeviceArray(len(v), rt.RAY_HIT, zero=True), len(v)) for k, v in sets.items()}
     variants = []
     for set_name in sets:
         for trav_name, trav in (("bounded", rt.TRAVERSAL_BOUNDED), ("kd", rt.TRAVERSAL_KD)):
@@ -78,44 +59,26 @@ def main():
     def launch(v):
         set_name, _, trav, _ = v
         rays, out, cnt = bufs[set_name]
-        assert hip.hipEventRecord(e0, stream) == 0
-        rt.trace_rays_device(run.dev, rays, cnt, out, traversal=trav, stream=stream.value)
-        assert hip.hipEventRecord(e1, stream) == 0
-        assert hip.hipEventSynchronize(e1) == 0
-        ms = ctypes.c_float()
-        assert hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1) == 0
-        return ms.value
+        return timer.span(lambda: rt.trace_rays_device(run.dev, rays, cnt, out, traversal=trav, stream=timer.s))[0]
 
     # the traversals must agree with each other before they are compared
     check = {}
     for v in variants:
         launch(v)
-        h = np.zeros(bufs[v[0]][2], rt.RAY_HIT)
-        rt.check(L.rt_download(h.ctypes.data, bufs[v[0]][1], h.nbytes))
+        h = bufs[v[0]][1].read()
         key = v[0]
         if key in check:
             assert np.array_equal(check[key].view(np.uint32), h.view(np.uint32)), v
         check[key] = h
-    for _ in range(a.warmup):
-        for v in variants:
-            launch(v)
-    times = {v: [] for v in variants}
-    for _ in range(a.reps):
-        for v in variants:
-            times[v].append(launch(v))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for v in variants:
-            t = np.array(times[v])
-            cnt = bufs[v[0]][2]
-            rec = {"scene": a.scene, "set": v[0], "rays": cnt, "traversal": v[1], "refill": v[3], "reps": a.reps,
-                   "ms_median": round(float(np.median(t)), 4), "ms_min": round(float(t.min()), 4),
-                   "ms_max": round(float(t.max()), 4),
-                   "mrays_per_s_median": round(cnt / float(np.median(t)) / 1e3, 1),
-                   "hit_fraction": round(float((check[v[0]]["triangle"] >= 0).mean()), 4)}
-            line = json.dumps(rec)
-            print(line, flush=True)
-            f.write(line + "\n")
+    times = gpu_timing.interleaved(variants, launch, a.warmup, a.reps)
+    records = []
+    for v in variants:
+        cnt = bufs[v[0]][2]
+        s = gpu_timing.summary(times[v], 4)
+        records.append({"scene": a.scene, "set": v[0], "rays": cnt, "traversal": v[1], "refill": v[3], **s,
+                        "mrays_per_s_median": round(cnt / float(np.median(times[v])) / 1e3, 1),
+                        "hit_fraction": round(float((check[v[0]]["triangle"] >= 0).mean()), 4)})
+    gpu_timing.write_lines(a.out, records)
 
 
 if __name__ == "__main__":

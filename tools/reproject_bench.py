@@ -21,15 +21,13 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in ("isaklm-raytracer_amd", "tests", "oracle"):
-    sys.path.insert(0, os.path.join(ROOT, p))
+import gpu_timing
+
 import helpers  # noqa: E402
 import rt  # noqa: E402
 
@@ -104,15 +102,12 @@ def error_lines(scene, W, H, K, S, configs):
 
 
 def spread(ms):
-    return {"median_ms": round(statistics.median(ms), 5), "min_ms": round(min(ms), 5), "max_ms": round(max(ms), 5),
-            "reps": len(ms)}
+    s = gpu_timing.summary(ms, 5)
+    return {"median_ms": s["ms_median"], "min_ms": s["ms_min"], "max_ms": s["ms_max"], "reps": s["reps"]}
 
 
 def timing_line(scene, W=1920, H=1080):
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-    hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    hip = gpu_timing.hip()
     L = rt.lib()
     n = W * H
     run = helpers.GpuRun(scene)
@@ -124,26 +119,18 @@ def timing_line(scene, W=1920, H=1080):
     bufs = []
 
     def guides(cam):
-        ptrs = []
-        for nbytes in (n * 4, n * 12, n * 4):
-            p = ctypes.c_void_p()
-            rt.check(L.rt_device_alloc(ctypes.byref(p), nbytes))
-            bufs.append(p)
-            ptrs.append(p)
-        b = rt.RtAovBuffers(ptrs[0], ptrs[1], None, ptrs[2])
+        ptrs = [rt.DeviceArray(n, np.float32), rt.DeviceArray((n, 3), np.float32), rt.DeviceArray(n, np.int32)]
+        bufs.extend(ptrs)
+        b = rt.RtAovBuffers(ptrs[0].p, ptrs[1].p, None, ptrs[2].p)
         rt.check(L.rt_render_aov(run.dev.prepared, cam, W, H, ctypes.byref(b), None))
         return ptrs
     ga, gb = guides(cam_a), guides(cam_b)
-    d_stats = ctypes.c_void_p()
-    rt.check(L.rt_device_alloc(ctypes.byref(d_stats), 24))
+    d_stats = rt.DeviceArray(3, np.uint64, zero=True)
     bufs.append(d_stats)
-    rt.check(L.rt_memset(d_stats, 0, 24))
     rt.reproject_device(g.g, ga, cam_a, gb, cam_b, W, H, out.g, stats=d_stats)
-    st = np.zeros(3, np.uint64)
-    rt.check(L.rt_download(rt._ptr(st), d_stats, 24))
-    s, e0, e1 = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(s)) == 0
-    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
+    st = d_stats.read()
+    timer = gpu_timing.Timer()
+    s = timer.stream
     arrays = [(out.g.frame_buffer, g.g.frame_buffer, n * 12), (out.g.squared_luminance, g.g.squared_luminance, n * 4),
               (out.g.sample_count, g.g.sample_count, n * 4)]
 
@@ -157,16 +144,14 @@ def timing_line(scene, W=1920, H=1080):
     def timed(work, name):
         rt.render(run.dev, busy, cam_a, 0, busy_opt)
         t = time.perf_counter()
-        assert hip.hipEventRecord(e0, s) == 0
+        timer.start()
         for _ in range(BATCH):
             work()
-        assert hip.hipEventRecord(e1, s) == 0
+        timer.stop()
         host_ms.setdefault(name, []).append((time.perf_counter() - t) * 1e3)
-        assert hip.hipStreamSynchronize(s) == 0
+        timer.synchronize()
         host_ms.setdefault(name + "_with_wait", []).append((time.perf_counter() - t) * 1e3)
-        ms = ctypes.c_float()
-        assert hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1) == 0
-        return ms.value / BATCH
+        return timer.elapsed_ms() / BATCH
 
     def do_reproject():
         rt.reproject_device(g.g, ga, cam_a, gb, cam_b, W, H, out.g, stream=s.value)
@@ -180,9 +165,9 @@ def timing_line(scene, W=1920, H=1080):
         if r >= WARMUP:
             t_rp.append(a)
             t_cp.append(b)
-    assert hip.hipEventDestroy(e0) == 0 and hip.hipEventDestroy(e1) == 0 and hip.hipStreamDestroy(s) == 0
-    for p in bufs:
-        L.rt_free(p)
+    timer.close()
+    for d in bufs:
+        d.free()
     g.free()
     out.free()
     busy.free()
@@ -193,7 +178,7 @@ def timing_line(scene, W=1920, H=1080):
             "reproject_over_copy": round(rp["median_ms"] / cp["median_ms"], 3),
             "unique_mb": round(n * 76 / 1e6, 1), "reproject_gb_s": round(n * 76 / rp["median_ms"] / 1e6, 1),
             "copy_gb_s": round(n * 40 / cp["median_ms"] / 1e6, 1), "history_kept": float(st[1]) / n,
-            "host_enqueue_ms_per_batch": {k: round(statistics.median(v), 3) for k, v in host_ms.items()}}
+            "host_enqueue_ms_per_batch": {k: gpu_timing.summary(v, 3)["ms_median"] for k, v in host_ms.items()}}
 
 
 def main():
@@ -208,8 +193,7 @@ def main():
     ap.add_argument("--no-error", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
-    if not helpers.gpu_has_device():
-        sys.exit("reproject_bench: no GPU (a measurement needs one)")
+    gpu_timing.require_device("reproject_bench")
     lines = []
     if not a.no_error:
         lines += error_lines(a.scene, a.size[0], a.size[1], a.frames, a.spp, [{}] + (GRID if a.sweep else []))

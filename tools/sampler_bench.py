@@ -26,16 +26,12 @@ usage: python tools/sampler_bench.py [--scene room2m] [--reps 10] [--warmup 2]
 """
 import argparse
 import ctypes
-import json
 import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "isaklm-raytracer_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
 
-import numpy as np  # noqa: E402
+import gpu_timing
+from gpu_timing import ROOT
 
 import helpers  # noqa: E402
 import rt  # noqa: E402
@@ -57,26 +53,12 @@ def main():
     n = W * H
 
     L = rt.lib()
-    if not helpers.gpu_has_device():
-        raise SystemExit("sampler_bench: no HIP device (nothing is measured without one)")
-    rt.check(L.rt_set_device(0))
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    hip.hipEventSynchronize.argtypes = [ctypes.c_void_p]
-    stream, e0, e1 = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    assert hip.hipStreamCreate(ctypes.byref(stream)) == 0
-    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
-
+    gpu_timing.require_device("sampler_bench")
+    timer = gpu_timing.Timer()
     run = helpers.GpuRun(a.scene)
     seeds = rt.seeds(n)
-
-    def dev(nbytes):
-        p = ctypes.c_void_p()
-        rt.check(L.rt_device_alloc(ctypes.byref(p), max(nbytes, 16)))
-        return p
-
-    d_rng, d_rad, d_sq, d_cnt, d_rays = dev(4 * n), dev(12 * n), dev(4 * n), dev(4 * n), dev(24 * n)
+    d_rng, d_rad, d_sq = rt.DeviceArray(n, np.uint32), rt.DeviceArray((n, 3), f32), rt.DeviceArray(n, f32)
+    d_cnt, d_rays = rt.DeviceArray(n, np.int32), rt.DeviceArray((n, 6), f32)
     kinds = {"pinhole": rt.Sampler("pinhole", W, H, run.camera), "equirect": rt.Sampler("equirect", W, H, run.camera)}
     host_rays = {kind: [] for kind in kinds}  # the uploaded variant's (rays, states after the draws) per sample
     variants = [(kind, how) for kind in kinds for how in ("fused", "unfused", "uploaded")]
@@ -84,46 +66,36 @@ def main():
     def launch(v):
         kind, how = v
         smp = kinds[kind]
-        rt.check(L.rt_upload(d_rng, seeds.ctypes.data, 4 * n))
-        t0 = time.perf_counter()
-        assert hip.hipEventRecord(e0, stream) == 0
-        if how == "fused":
-            rt.sample_paths_device(run.dev, smp, d_rng, n, d_rad, d_sq, d_cnt, samples=SAMPLES, stream=stream.value)
-        else:
+        d_rng.upload(seeds)
+
+        def work():
+            if how == "fused":
+                rt.sample_paths_device(run.dev, smp, d_rng, n, d_rad, d_sq, d_cnt, samples=SAMPLES, stream=timer.s)
+                return
             for k in range(SAMPLES):
                 if how == "unfused":
                     s = smp.struct()
-                    rt.check(L.rt_sampler_rays(ctypes.byref(s), d_rng, n, d_rays, stream))
+                    rt.check(L.rt_sampler_rays(ctypes.byref(s), d_rng, n, d_rays, timer.stream))
                 else:
                     # the host's rays of this sample, and the states after their draws (4 B per pixel more), so
-                    # that this variant computes the fused one's result bit for bit
+                    # that this variant computes the fused one's result bit for bit (the bare copies: this is timed)
                     rt.check(L.rt_upload(d_rays, host_rays[kind][k][0].ctypes.data, 24 * n))
                     rt.check(L.rt_upload(d_rng, host_rays[kind][k][1].ctypes.data, 4 * n))
                 rt.trace_paths_device(run.dev, d_rays, d_rng, n, d_rad, d_sq, samples=1, accumulate=k > 0,
-                                      stream=stream.value)
-        assert hip.hipEventRecord(e1, stream) == 0
-        assert hip.hipEventSynchronize(e1) == 0
-        wall = (time.perf_counter() - t0) * 1e3
-        ms = ctypes.c_float()
-        assert hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1) == 0
-        return ms.value, wall
+                                      stream=timer.s)
+        return timer.span(work)
 
     def results():
-        out = [np.zeros((n, 3), f32), np.zeros(n, f32), np.zeros(n, np.uint32)]
-        for arr, p in zip(out, (d_rad, d_sq, d_rng)):
-            rt.check(L.rt_download(arr.ctypes.data, p, arr.nbytes))
-        return out
+        return [d_rad.read(), d_sq.read(), d_rng.read()]
 
     # the uploaded variant's rays, made ahead of time: sample k's start from the states sample k - 1's paths left
     for kind, smp in kinds.items():
-        rt.check(L.rt_upload(d_rng, seeds.ctypes.data, 4 * n))
+        d_rng.upload(seeds)
         for k in range(SAMPLES):
-            st = np.zeros(n, np.uint32)
-            rt.check(L.rt_download(st.ctypes.data, d_rng, 4 * n))
-            rays, after = rt.sampler_rays_host(smp, st)
+            rays, after = rt.sampler_rays_host(smp, d_rng.read())
             host_rays[kind].append((rays, after))
-            rt.check(L.rt_upload(d_rays, rays.ctypes.data, 24 * n))
-            rt.check(L.rt_upload(d_rng, after.ctypes.data, 4 * n))
+            d_rays.upload(rays)
+            d_rng.upload(after)
             rt.trace_paths_device(run.dev, d_rays, d_rng, n, d_rad, d_sq, samples=1, accumulate=k > 0)
 
     # the three variants of a kind must agree before they are compared
@@ -136,29 +108,18 @@ def main():
                 assert np.array_equal(arr.view(np.uint32), ref.view(np.uint32)), f"{kind} {how}: {what} differs from fused"
         assert (want[0] != 0).any(axis=1).mean() > 0.10
 
-    for _ in range(a.warmup):
-        for v in variants:
-            launch(v)
-    times = {v: [] for v in variants}
-    for _ in range(a.reps):
-        for v in variants:
-            times[v].append(launch(v))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for v in variants:
-            t = np.array([x[0] for x in times[v]])
-            wall = np.array([x[1] for x in times[v]])
-            med = float(np.median(t))
-            base = float(np.median([x[0] for x in times[(v[0], "unfused")]]))
-            rec = {"scene": a.scene, "sampler": v[0], "variant": v[1], "width": W, "height": H, "samples": SAMPLES,
-                   "paths": n * SAMPLES, "reps": a.reps, "ms_median": round(med, 3), "ms_min": round(float(t.min()), 3),
-                   "ms_max": round(float(t.max()), 3), "spread": round(float(t.max() - t.min()) / med, 4),
-                   "host_ms_median": round(float(np.median(wall)), 3),
-                   "mpaths_per_s_median": round(n * SAMPLES / med / 1e3, 2), "time_over_unfused": round(med / base, 4),
-                   "equals_fused_bitwise": True}
-            line = json.dumps(rec)
-            print(line, flush=True)
-            f.write(line + "\n")
+    times = gpu_timing.interleaved(variants, launch, a.warmup, a.reps)
+    records = []
+    for v in variants:
+        t = [x[0] for x in times[v]]
+        med = float(np.median(t))
+        base = float(np.median([x[0] for x in times[(v[0], "unfused")]]))
+        records.append({"scene": a.scene, "sampler": v[0], "variant": v[1], "width": W, "height": H, "samples": SAMPLES,
+                        "paths": n * SAMPLES, **gpu_timing.summary(t, 3),
+                        "host_ms_median": round(float(np.median([x[1] for x in times[v]])), 3),
+                        "mpaths_per_s_median": round(n * SAMPLES / med / 1e3, 2),
+                        "time_over_unfused": round(med / base, 4), "equals_fused_bitwise": True})
+    gpu_timing.write_lines(a.out, records)
 
 
 if __name__ == "__main__":

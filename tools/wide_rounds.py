@@ -17,8 +17,6 @@ import json
 import os
 import sys
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "isaklm-raytracer_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import helpers  # noqa: E402
@@ -37,8 +35,7 @@ if len(sys.argv) > 3 and sys.argv[3] == "bounded":
                                                      counters=cnt.p, traversal=rt.TRAVERSAL_BOUNDED_COUNTED,
                                                      debug=rt.DEBUG_COUNT_LONG_ONLY))
     rt.join()
-    a = np.zeros(rt.N_COUNTERS, dtype=np.uint64)
-    rt.check(rt.lib().rt_download(rt._ptr(a), cnt.p, a.nbytes))
+    a = cnt.words.read()
     kd_nodes, kd_tests, rays, calls, rounds, wnodes, wtests, bary = (int(a[i]) for i in (0, 1, 7, 22, 23, 37, 38, 39))
     dev = rt.deviation_stats()
     q = max(calls, 1)
@@ -53,8 +50,7 @@ if len(sys.argv) > 3 and sys.argv[3] == "bounded":
 rt.render(run.dev, g, run.camera, 0, rt.options(W, H, passes, adaptive=False, kernel=rt.KERNEL_WAVEFRONT,
                                                  counters=cnt.p))
 rt.join()
-a = np.zeros(rt.N_COUNTERS, dtype=np.uint64)
-rt.check(rt.lib().rt_download(rt._ptr(a), cnt.p, a.nbytes))
+a = cnt.words.read()
 calls, rounds, t, tl, tf, te = (int(a[i]) for i in (22, 23, 24, 25, 26, 27))
 print(json.dumps({"scene": scene, "passes": passes, "wide_calls": calls, "rounds": rounds,
                   "rounds_per_call": round(rounds / max(calls, 1), 2),
